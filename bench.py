@@ -8,9 +8,11 @@ embeddings -> exact cosine top-500 row ids + scores.  With --gpus P > 1 the SAME
 row-sharded over the ranks (strong scaling): per-shard top-k, one RCCL all-gather of the packed
 [Q, k] lists, merge on every rank, batches alternating between two pipeline lanes.
 
-Prints ONE JSON line on rank 0: `value` / `roofline` / `cpu_baseline` for the f32 scan, plus extra objects that are
-not part of `value`: `two_stage` (the same batches through the f16-shadow + f32 re-scoring scan, checked bit for bit
-against the f32 scan), `graph_eval` (scorer + metrics + evaluation loop), `encode` (text-encoding stage).
+Prints ONE JSON line on rank 0: `value` / `roofline` for the f32 scan.  A plain run does only that: it sets up, warms up,
+times the --steps steps and prints the line.  `--full` adds every leg that is not part of `value`: `cpu_baseline`,
+`sustained`, `two_stage` (the same batches through the f16-shadow + f32 re-scoring scan, checked bit for bit against the
+f32 scan), the BASELINE config legs, `graph_eval` (scorer + metrics + evaluation loop), `encode` (text-encoding stage) and
+`end_to_end`.  `--dump-outputs DIR` writes the last timed step's top-k (DIR/scores.npy, DIR/ids.npy).
 """
 from __future__ import annotations
 
@@ -109,12 +111,71 @@ def parse_args():
                     help="seconds a collective (or the rendezvous) may take before the process group aborts the rank")
     ap.add_argument("--deadline", type=float, default=2700.0,
                     help="seconds after which a rank that is still running gives up with exit code 124 (a hang must not outlive the run)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg that is not part of the headline figure (CPU baselines, sustained and two-stage legs, "
+                         "the BASELINE config legs, graph_eval, encode, end_to_end); without it only the headline leg runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's top-k: DIR/scores.npy (f32) and DIR/ids.npy (f64)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.graph_kernels:
+        ap.error("--dump-outputs writes the top-k leg's results; --graph-kernels runs no top-k leg")
+    if not args.full:
+        # a plain run: set up, warm up, time the steps of the headline leg, print its line — nothing else
+        args.no_cpu_baseline = args.no_two_stage = args.no_graph_eval = args.no_encode = args.no_extra_legs = True
+    return args
+
+
+# ---- the synthetic inputs: the same bits in every run and on every device --------------------------------------------
+# torch's device generators are no use here: randn / randint cap their grid at a multiple of the device's CU count and
+# derive each element's Philox stream from its thread index, so a device with another CU count draws other numbers.
+# Every input value below is a hash of (key, element index) computed with elementwise integer ops instead.
+_M32 = 0xFFFFFFFF
+
+
+def _mul32(x, m):
+    """x * m mod 2^32 for 32-bit values held in int64 (the product is split so that it never leaves int64)."""
+    return (x * (m & 0xFFFF) + (((x * (m >> 16)) & 0xFFFF) << 16)) & _M32
+
+
+def _mix32(x):
+    """A bijective 32-bit finaliser (xor-shift / multiply, "lowbias32"); works on Python ints and int64 tensors."""
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def counter_bits(key, n, dev):
+    """n pseudo-random 32-bit words (int64 tensor on `dev`); word i depends only on `key` (a tuple of ints) and i."""
+    if n >= 1 << 32:
+        raise ValueError(f"counter_bits: {n} words exceed the 32-bit counter")
+    k = 0
+    for w in key:
+        for part in (w & _M32, (w >> 32) & _M32):
+            k = _mix32(((k ^ part) + 0x9E3779B9) & _M32)
+    k2 = _mix32(k ^ 0x85EBCA6B)
+    return _mix32(_mix32(torch.arange(n, dtype=torch.int64, device=dev) ^ k) ^ k2)
+
+
+def counter_normal(key, n, dev):
+    """n N(0, 1) f32 values from counter_bits (Box-Muller in f64 on two words per value)."""
+    b = counter_bits(key, 2 * n, dev).view(n, 2).double()
+    r = torch.sqrt(-2.0 * torch.log((b[:, 0] + 1.0) * 2.0 ** -32))
+    return (r * torch.cos(b[:, 1] * (2.0 * np.pi * 2.0 ** -32))).float()
+
+
+def last_draw_per_destination(dst):
+    """(destinations, index of the draw that writes each): a row drawn twice takes the LATER draw, as a sequential loop
+    would.  `t[dst] = v` with repeated indices lets any writer win, element by element, so it is never used as is."""
+    u, inv = torch.unique(dst, return_inverse=True)
+    last = torch.full((u.numel(),), -1, dtype=torch.int64, device=dst.device)
+    return u, last.scatter_reduce_(0, inv, torch.arange(dst.numel(), device=dst.device), "amax")
 
 
 def build_shard(dev, row_begin, row_end, D, seed, dtype=torch.float32):
     """Rows [row_begin, row_end) of the global synthetic index, generated chunk-wise on the GPU so
-    that the content of a global row does not depend on the number of ranks.  N(0,1) entries,
+    that the content of a global row does not depend on the number of ranks.  N(0,1) entries (counter_normal),
     global row 0 all-zero (eps clamp), 1 % of each chunk's rows duplicated (exact ties).  Every chunk is
     normalised (C1) and stored in `dtype` as it is made, so a 100 M-row f16 index (154 GB, BASELINE config 4) is
     built on one 288 GB GPU without ever holding its f32 form.  dtype "fp8": every chunk is quantised as it is made
@@ -128,14 +189,13 @@ def build_shard(dev, row_begin, row_end, D, seed, dtype=torch.float32):
     scale = torch.empty(n, dtype=torch.float32, device=dev) if fp8 else None
     c0 = row_begin // CHUNK_ROWS
     c1 = (row_end + CHUNK_ROWS - 1) // CHUNK_ROWS
-    gen = torch.Generator(device=dev)
     for c in range(c0, c1):
-        gen.manual_seed(seed * 1_000_003 + c)
-        chunk = torch.randn((CHUNK_ROWS, D), generator=gen, device=dev, dtype=torch.float32)
+        key = seed * 1_000_003 + c
+        chunk = counter_normal((key, 0), CHUNK_ROWS * D, dev).view(CHUNK_ROWS, D)
         ndup = CHUNK_ROWS // 100
-        src = torch.randint(1, CHUNK_ROWS, (ndup,), generator=gen, device=dev)
-        dst = torch.randint(1, CHUNK_ROWS, (ndup,), generator=gen, device=dev)
-        chunk[dst] = chunk[src]
+        src = 1 + counter_bits((key, 1), ndup, dev) % (CHUNK_ROWS - 1)
+        dst, last = last_draw_per_destination(1 + counter_bits((key, 2), ndup, dev) % (CHUNK_ROWS - 1))
+        chunk[dst] = chunk[src[last]]
         if c == 0:
             chunk[0] = 0.0
         ops.normalize_embeddings(chunk, EPS, out=chunk)  # C1, in place: the resident index is normalised
@@ -174,9 +234,7 @@ def build_queries(dev, shard, row_begin, row_end, n_total, n_batches, Q, D, seed
         base[mine.to(dev)] = rows.float()
     if world > 1:
         all_reduce_(base, dist.ReduceOp.SUM)
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(seed * 7 + 12345)
-    noise = torch.randn((n_batches, Q, D), generator=gen, device=dev, dtype=torch.float32)
+    noise = counter_normal((seed * 7 + 12345, 3), n_batches * Q * D, dev).view(n_batches, Q, D)
     q = base + 0.5 * noise / (D ** 0.5)
     q = ops.normalize_embeddings(q.view(-1, D), EPS).view(n_batches, Q, D)
     return q, gold
@@ -215,6 +273,25 @@ def pmc_traffic(N, D, Q, k, world, kernel_ms_per_step, method="scan"):
     return {"traffic": best["hbm_bytes_per_step"] / (kernel_ms_per_step * 1e-3) / 1e9,
             "traffic_source": f"profiles/{best_name}: committed rocprofv3 --pmc passes ({best['hbm_bytes_per_step']} HBM bytes per step), "
                               "rescaled by this run's kernel time; not read live"}
+
+
+DUMP_MAX_BYTES = 60 << 20  # --dump-outputs writes at most this much array data
+
+
+def dump_outputs(out_dir, scores, ids, seed):
+    """--dump-outputs: what a caller of ShardedIndex.topk_async receives for the last timed batch, the [Q, k] scores (f32)
+    and global row ids (f64, exact below 2^53).  A result above DUMP_MAX_BYTES is written for a fixed seeded sample of the
+    query rows, whose indices go to query_rows.npy."""
+    s = scores.float().cpu().numpy()
+    i = ids.cpu().numpy().astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    per_row = s.shape[1] * (s.itemsize + i.itemsize) + 8
+    if s.shape[0] * per_row > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(seed).choice(s.shape[0], DUMP_MAX_BYTES // per_row, replace=False))
+        s, i = s[rows], i[rows]
+        np.save(os.path.join(out_dir, "query_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "scores.npy"), s)
+    np.save(os.path.join(out_dir, "ids.npy"), i)
 
 
 def exact_env():
@@ -1208,10 +1285,11 @@ class Ctx:
 
 
 def run_index_leg(ctx, *, N, D, Q, k, index_dtype, method, steps, warmup, seed, want_two_stage=False, sustained_s=0.0,
-                  cpu_rows=0, cpu_seconds=0.0, workload=None, fp8_mfma=False, fp8_ab=False, many_query=0):
+                  cpu_rows=0, cpu_seconds=0.0, workload=None, fp8_mfma=False, fp8_ab=False, many_query=0, dump_dir=None):
     """One index configuration end to end: build the (sharded) resident index in its storage type, W untimed + K timed
     steps through ShardedIndex.topk_async, live kernel times (hipExtLaunchKernelGGL events inside the library), planted-row
-    Hits@k.  Returns the JSON object of the leg (complete on rank 0)."""
+    Hits@k.  Returns the JSON object of the leg (complete on rank 0).  `dump_dir`: rank 0 writes the last timed step's
+    result there (dump_outputs)."""
     import ctypes
 
     from evi_rag_amd import _lib, ops
@@ -1332,6 +1410,8 @@ def run_index_leg(ctx, *, N, D, Q, k, index_dtype, method, steps, warmup, seed, 
         return shard_rows * D * 2 + Q * D * 4 + Q * kk * 12
 
     elapsed, ms, launches, out = timed_run(index)
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, out[0], out[1], seed)
     # two_stage: a batch whose proof fails is re-done by the gated f32 scan on the device, so the results are exact
     # either way; the flag (max over ranks, a collective) only says that such repairs happened inside the timed region
     two_stage_fallback = index.two_stage_failed() if method == "two_stage" else False
@@ -1660,7 +1740,7 @@ def main():
     result = run_index_leg(ctx, N=args.rows, D=args.dim, Q=args.queries, k=args.k, index_dtype=args.index_dtype,
                            method=args.topk_method, steps=args.steps, warmup=args.warmup, seed=args.seed,
                            want_two_stage=not args.no_two_stage, sustained_s=2.0 if extra else 0.0,
-                           cpu_rows=args.cpu_rows, cpu_seconds=cpu_s, fp8_mfma=args.fp8_mfma)
+                           cpu_rows=args.cpu_rows, cpu_seconds=cpu_s, fp8_mfma=args.fp8_mfma, dump_dir=args.dump_outputs)
     # ---- N > 1: the BASELINE scaling target is quoted on the 100 M-triple index (configs[3]) — measure THAT, row-sharded
     # over the ranks of this run, and configs[4] (e4m3, D = 1024, native fp8 MFMA) the same way.  Every rank takes part
     # (the legs are collective); rank 0 holds the objects.  N = 1 runs the same index whole on the one GPU (`config4_full`

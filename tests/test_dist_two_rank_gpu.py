@@ -101,7 +101,7 @@ def test_bench_two_rank_control_flow_on_one_gpu(dev):
     env["EVI_BENCH_BACKEND"] = "gloo"
     root = os.path.dirname(HERE)
     small = ["--steps", "4", "--warmup", "2", "--rows", "300001", "--dim", "128", "--k", "50", "--no-cpu-baseline",
-             "--no-graph-eval", "--no-encode", "--no-extra-legs"]
+             "--no-graph-eval", "--no-encode", "--no-extra-legs", "--full"]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
                         "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2"] + small,
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=800)
@@ -141,7 +141,7 @@ def test_bench_two_rank_config4_and_config5_sharded_legs(dev):
     `config5_sharded` leg (configs[4]: e4m3 index, native fp8 MFMA) — here with a miniature row count, two ranks on the one
     GPU, gloo + host-staged exchange (replaces src/callbacks/retriever_topk_edge_writer.py:450-462)."""
     line = _rehearse({}, ["--steps", "4", "--warmup", "2", "--rows", "200001", "--dim", "128", "--k", "50", "--no-cpu-baseline",
-                          "--no-graph-eval", "--no-encode", "--config4-rows", "300001"])
+                          "--no-graph-eval", "--no-encode", "--config4-rows", "300001", "--full"])
     for key, D, dt in (("config4_sharded", 768, "f16"), ("config5_sharded", 1024, "fp8")):
         leg = line[key]
         assert leg["ranks_seen"] == 2 and leg["n_gpus"] == 2 and leg["config"]["sharding"] == "rows/2"
@@ -160,7 +160,7 @@ def test_bench_two_rank_graph_eval_sharded_leg(dev):
     """N > 1 also measures the per-question stage sharded by question (graphs never span ranks, counters summed
     with one all-reduce): every rank evaluates its own split, the line carries the aggregate."""
     line = _rehearse({}, ["--steps", "3", "--warmup", "1", "--rows", "100001", "--dim", "64", "--k", "20", "--no-cpu-baseline",
-                          "--no-encode", "--config4-rows", "100001", "--eval-shard-questions", "64"])
+                          "--no-encode", "--config4-rows", "100001", "--eval-shard-questions", "64", "--full"])
     ge = line["graph_eval_sharded"]
     assert "skipped" not in ge, ge
     assert ge["n_gpus"] == 2 and ge["questions"] == 128 and ge["scaling"] == "weak" and ge["value"] > 0
@@ -176,7 +176,7 @@ def test_bench_two_rank_lane_failure_falls_back_in_process(dev, where):
     stay exact — the run neither hangs nor dies."""
     line = _rehearse({"EVI_INJECT_LANE_FAILURE": where},
                      ["--steps", "4", "--warmup", "2", "--rows", "200001", "--dim", "128", "--k", "50", "--no-cpu-baseline",
-                      "--no-graph-eval", "--no-encode", "--no-extra-legs"])
+                      "--no-graph-eval", "--no-encode", "--no-extra-legs", "--full"])
     pipe = line["config"]["pipeline"]
     assert "FALLBACK from two lanes" in pipe and "injected" in pipe and "one communicator" in pipe
     assert line["ranks_seen"] == 2 and line["hits_at_k"]["hits@1"] == 1.0 and line["hits_at_k"]["hits@50"] == 1.0 and line["sorted_ok"]

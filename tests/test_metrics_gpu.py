@@ -172,14 +172,13 @@ def test_feature_monitor_matches_reference_golden(dev):
     np.testing.assert_allclose([float(out[k]) for k in sorted(out)], z["nopos_values"], rtol=2e-6, atol=2e-7)
 
 
-def test_compute_ranking_metrics_matches_the_reference_function_and_the_oracle():
+def test_compute_ranking_metrics_matches_the_reference_function_and_the_oracle(dev):
     """src/utils/metrics.py:112-170 (compute_ranking_metrics, _ndcg): golden = the reference's own function on seeded samples
     (binary and graded labels, all-positive / all-negative / one-element samples, k beyond the sample length)."""
     from evi_rag_amd import metrics as M
 
     z = np.load(os.path.join(GOLD, "ranking_metrics.npz"), allow_pickle=False)
     ptr, ks = z["ptr"], [int(k) for k in z["k_values"]]
-    dev = torch.device("cuda:0")
     samples = [{"scores": torch.from_numpy(z["scores"][a:b]).to(dev), "labels": torch.from_numpy(z["labels"][a:b]).to(dev)}
                for a, b in zip(ptr[:-1], ptr[1:])]
     st = M.compute_ranking_metrics(samples, ks)

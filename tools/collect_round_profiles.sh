@@ -12,8 +12,8 @@ cd /tmp && export TMPDIR=/tmp
 SMALL="--steps 3 --warmup 1 --no-cpu-baseline --no-graph-eval --no-encode --no-extra-legs"
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
 
-# 1. per-kernel time of the default bench command
-rocprofv3 --kernel-trace --stats --output-format csv -d $S/stats -o bench -- python3 $R/bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_profiled.json 2> $O/bench_profiled.err || exit 1
+# 1. per-kernel time of the full bench command (every leg)
+rocprofv3 --kernel-trace --stats --output-format csv -d $S/stats -o bench -- python3 $R/bench.py --steps 20 --warmup 5 --full > $O/${TAG}_bench_profiled.json 2> $O/bench_profiled.err || exit 1
 cp $S/stats/bench_kernel_stats.csv $O/${TAG}_bench_kernel_stats.csv
 # 1b. the headline leg alone (every launch of the scan kernel has the headline shape: the table's average x 3 = kernel_ms_per_step)
 rocprofv3 --kernel-trace --stats --output-format csv -d $S/stats_h -o bench -- python3 $R/bench.py --steps 20 --warmup 5 --no-two-stage --no-cpu-baseline --no-graph-eval --no-encode --no-extra-legs > $O/${TAG}_bench_headline_only.json 2> $O/bench_headline.err || exit 1
@@ -65,7 +65,7 @@ cp $S/st_train/s_kernel_stats.csv $O/${TAG}_train_step_kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d $S/st_fwd -o s -- python3 $R/tools/scorer_forward_profile.py full > /dev/null 2> $O/st_fwd.err || exit 6
 cp $S/st_fwd/s_kernel_stats.csv $O/${TAG}_scorer_forward_kernel_stats.csv
 for B in 32 512; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $S/st_g$B -o s -- python3 $R/bench.py --graph-kernels --graph-batch $B --steps 20 --warmup 5 > $O/${TAG}_config3_graph_kernels_b$B.json 2> $O/st_g$B.err || exit 7
+  rocprofv3 --kernel-trace --stats --output-format csv -d $S/st_g$B -o s -- python3 $R/bench.py --graph-kernels --graph-batch $B --steps 20 --warmup 5 --full > $O/${TAG}_config3_graph_kernels_b$B.json 2> $O/st_g$B.err || exit 7
   cp $S/st_g$B/s_kernel_stats.csv $O/${TAG}_config3_graph_kernels_b${B}_kernel_stats.csv
 done
 echo "graph done"
