@@ -37,6 +37,16 @@ int fail(int code, const char* fmt, ...);
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Workspace layouts: hands out 256-byte-aligned slices in call order; `total` is the bytes handed out so far.
+struct Bump {
+    size_t total = 0;
+    size_t take(size_t bytes) {
+        const size_t at = total;
+        total = align_up(total + bytes, 256);
+        return at;
+    }
+};
+
 // ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------
 // When enabled, launch sites bracket their dominant kernel with hipEvents on the call's stream;
 // evi_timing_read() synchronises those events and returns the summed durations per class.

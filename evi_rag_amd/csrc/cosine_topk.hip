@@ -1009,23 +1009,18 @@ struct GtLayout {
 
 static GtLayout gt_layout(int Q, int64_t N, int D, int k, int single = 1 /* the larger reserve */) {
     GtLayout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
+    Bump m;
     const int kk = gemm_topk_reserve(k, single) <= EVI_TOPK_MAX_K ? gemm_topk_reserve(k, single) : gemm_topk_reserve(k, 0);
     L.slab = N < kGemmSlabRows ? (N > 0 ? N : 1) : kGemmSlabRows;
     const int64_t first = N < kGemmFirstRows ? (N > 0 ? N : 1) : kGemmFirstRows;
-    L.tau = take((size_t)Q * sizeof(float));
-    L.cnt = take((size_t)Q * kCntStride * sizeof(int32_t));
-    L.cs = take((size_t)Q * kGemmTopkCap * sizeof(float));
-    L.ci = take((size_t)Q * kGemmTopkCap * sizeof(int32_t));
-    L.exact = take((size_t)Q * kk * sizeof(float));
-    L.scores = take((size_t)first * Q * sizeof(float));  // only the first slab's scores are materialised
-    L.wsplit = take(gemm_bf16x3_workspace_bytes(Q, D));
-    L.total = off;
+    L.tau = m.take((size_t)Q * sizeof(float));
+    L.cnt = m.take((size_t)Q * kCntStride * sizeof(int32_t));
+    L.cs = m.take((size_t)Q * kGemmTopkCap * sizeof(float));
+    L.ci = m.take((size_t)Q * kGemmTopkCap * sizeof(int32_t));
+    L.exact = m.take((size_t)Q * kk * sizeof(float));
+    L.scores = m.take((size_t)first * Q * sizeof(float));  // only the first slab's scores are materialised
+    L.wsplit = m.take(gemm_bf16x3_workspace_bytes(Q, D));
+    L.total = m.total;
     return L;
 }
 
@@ -1282,19 +1277,14 @@ struct TsLayout {
 static TsLayout ts_layout(int Q, int64_t N, int D, int k) {
     TsLayout L;
     const int kk = two_stage_kk(k);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    L.flag = take(sizeof(int32_t));  // this call's proof flag (gate of the device-side fallback)
-    L.approx = take((size_t)Q * kk * sizeof(float));
-    L.ids = take((size_t)Q * kk * sizeof(int64_t));
-    L.exact = take((size_t)Q * kk * sizeof(float));
+    Bump m;
+    L.flag = m.take(sizeof(int32_t));  // this call's proof flag (gate of the device-side fallback)
+    L.approx = m.take((size_t)Q * kk * sizeof(float));
+    L.ids = m.take((size_t)Q * kk * sizeof(int64_t));
+    L.exact = m.take((size_t)Q * kk * sizeof(float));
     L.scan_bytes = evi_cosine_topk_workspace_bytes(Q, N, D, kk);
-    L.scan = take(L.scan_bytes);
-    L.total = off;
+    L.scan = m.take(L.scan_bytes);
+    L.total = m.total;
     return L;
 }
 

@@ -637,35 +637,41 @@ static int scorer_gemm(const float* A, int64_t M, int K, int64_t lda, const floa
 // Everything the forward derives from the WEIGHTS alone, kept across calls by callers whose weights do not change between
 // forwards (evaluation): the column blocks of state_net.0, the transposed struct_proj weight, the folded head, and the
 // bf16 hi / lo planes of the nine GEMM weights.  ~25 small launches per forward otherwise.
+// The f32 section (WeightDerived) is also part of the forward workspace, where a forward without a prepared buffer makes it.
+struct WeightDerived {
+    size_t wa, wb, wc, wd, wt, vhead, fold;
+};
+static WeightDerived place_weight_derived(Bump& m, int D, int H, int F) {
+    WeightDerived W;
+    const size_t f = sizeof(float);
+    W.wa = m.take((size_t)H * D * f);
+    W.wb = m.take((size_t)H * D * f);
+    W.wc = m.take((size_t)H * D * f);
+    W.wd = m.take((size_t)H * f);
+    W.wt = m.take((size_t)F * D * f);
+    W.vhead = m.take((size_t)(H + 1) * f);
+    W.fold = m.take((size_t)32 * H * f);  // kFoldSlices partial rows of the folded head
+    return W;
+}
+
 struct PrepLayout {
-    size_t wa, wb, wc, wd, wt, vhead, fold, p_entity, p_query, p_gate, p_bias, p_rel, p_wa, p_wb, p_wc, p_s4, total;
+    WeightDerived wts;
+    size_t p_entity, p_query, p_gate, p_bias, p_rel, p_wa, p_wb, p_wc, p_s4, total;
 };
 static PrepLayout prep_layout(int D, int H, int F) {
     PrepLayout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    const size_t f = sizeof(float);
-    L.wa = take((size_t)H * D * f);
-    L.wb = take((size_t)H * D * f);
-    L.wc = take((size_t)H * D * f);
-    L.wd = take((size_t)H * f);
-    L.wt = take((size_t)F * D * f);
-    L.vhead = take((size_t)(H + 1) * f);
-    L.fold = take((size_t)32 * H * f);
-    L.p_entity = take(gemm_bf16x3_workspace_bytes(D, D));
-    L.p_query = take(gemm_bf16x3_workspace_bytes(D, D));
-    L.p_gate = take(gemm_bf16x3_workspace_bytes(D, D));
-    L.p_bias = take(gemm_bf16x3_workspace_bytes(D, D));
-    L.p_rel = take(gemm_bf16x3_workspace_bytes(D, D));
-    L.p_wa = take(gemm_bf16x3_workspace_bytes(H, D));
-    L.p_wb = take(gemm_bf16x3_workspace_bytes(H, D));
-    L.p_wc = take(gemm_bf16x3_workspace_bytes(H, D));
-    L.p_s4 = take(gemm_bf16x3_workspace_bytes(H, H));
-    L.total = off;
+    Bump m;
+    L.wts = place_weight_derived(m, D, H, F);
+    L.p_entity = m.take(gemm_bf16x3_workspace_bytes(D, D));
+    L.p_query = m.take(gemm_bf16x3_workspace_bytes(D, D));
+    L.p_gate = m.take(gemm_bf16x3_workspace_bytes(D, D));
+    L.p_bias = m.take(gemm_bf16x3_workspace_bytes(D, D));
+    L.p_rel = m.take(gemm_bf16x3_workspace_bytes(D, D));
+    L.p_wa = m.take(gemm_bf16x3_workspace_bytes(H, D));
+    L.p_wb = m.take(gemm_bf16x3_workspace_bytes(H, D));
+    L.p_wc = m.take(gemm_bf16x3_workspace_bytes(H, D));
+    L.p_s4 = m.take(gemm_bf16x3_workspace_bytes(H, H));
+    L.total = m.total;
     return L;
 }
 
@@ -684,10 +690,43 @@ static int dpl_for(int d) {
         default: { constexpr int DPL = 5; CALL; } break;  \
     }
 
+// The node-level results of the forward: projected nodes / questions / relations, the structure features, both CSR halves
+// and node_repr Wc^T.  The first section of the forward workspace; a training forward keeps a copy of the same layout behind
+// the per-edge rows of `saved` when the caller's buffer has room (evi_retriever_saved_bytes_full), and the backward then
+// starts from it instead of recomputing the node-level forward (three large GEMMs, the CSR build, DDE, the relation
+// de-duplication: ~0.6 ms of a 13.6 ms step at the bench shape).
+struct NodeKeep {
+    size_t node_repr, non_text, q_proj, gate_q, bias_q, rel_repr, rel_rows, ns, in_ptr, in_nbr, in_eid, out_ptr, out_nbr, out_eid, hcn, total;
+};
+static NodeKeep node_keep_layout(int64_t N, int64_t E, int B, int D, int H, int F, int64_t R, int dedupe) {
+    NodeKeep K;
+    Bump m;
+    const size_t f = sizeof(float);
+    const size_t n1 = (size_t)(N > 0 ? N : 1), e1 = (size_t)(E > 0 ? E : 1);
+    K.node_repr = m.take(n1 * D * f);
+    K.non_text = m.take((size_t)D * f);
+    K.q_proj = m.take((size_t)B * D * f);
+    K.gate_q = m.take((size_t)B * D * f);
+    K.bias_q = m.take((size_t)B * D * f);
+    K.rel_repr = m.take((size_t)(dedupe ? R : e1) * D * f);
+    K.rel_rows = m.take(dedupe ? (size_t)R * D * f : 256);
+    K.ns = m.take(n1 * (F / 2) * f);
+    K.in_ptr = m.take((size_t)(N + 1) * 4);
+    K.in_nbr = m.take(e1 * 4);
+    K.in_eid = m.take(e1 * 4);
+    K.out_ptr = m.take((size_t)(N + 1) * 4);
+    K.out_nbr = m.take(e1 * 4);
+    K.out_eid = m.take(e1 * 4);
+    K.hcn = m.take(n1 * H * f);
+    K.total = m.total;
+    return K;
+}
+
 struct FwdLayout {
-    size_t node_repr, non_text, q_proj, gate_q, bias_q, rel_repr, rel_rows, rel_first, status, ns, in_ptr, in_nbr,
-        in_eid, out_ptr, out_nbr, out_eid, csr_ws, wa, wb, wc, wd, vhead, fold, wt, wsplit, hcn, P, RCX, XS, aux, PA, RC, SB,
-        h1n, pair_table, pair_count, pair_key, pair_rcx, pair_rc, total;
+    NodeKeep node;      // at offset 0: the same offsets as the copy kept in `saved`
+    WeightDerived wts;  // unused when the caller passes a prepared buffer
+    size_t rel_first, status, csr_ws, wsplit, P, RCX, XS, aux, PA, RC, SB, h1n, pair_table, pair_count, pair_key, pair_rcx,
+        pair_rc, total;
     int64_t ec, pair_max;  // pair_max: bound on the (relation, graph) pairs of a batch, 0 = the per-edge form
     int dedupe;
 };
@@ -702,59 +741,82 @@ constexpr int64_t kPairTableMax = (int64_t)1 << 22;
 
 static FwdLayout fwd_layout(int64_t N, int64_t E, int B, int D, int H, int F, int64_t R, int dirs) {
     FwdLayout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
     L.dedupe = (R > 0 && R <= E) ? 1 : 0;
     L.ec = E < edge_chunk() ? (E > 0 ? E : 1) : edge_chunk();
+    L.node = node_keep_layout(N, E, B, D, H, F, R, L.dedupe);
+    Bump m{L.node.total};
     const size_t f = sizeof(float);
-    const size_t n1 = (size_t)(N > 0 ? N : 1), e1 = (size_t)(E > 0 ? E : 1);
-    L.node_repr = take(n1 * D * f);
-    L.non_text = take((size_t)D * f);
-    L.q_proj = take((size_t)B * D * f);
-    L.gate_q = take((size_t)B * D * f);
-    L.bias_q = take((size_t)B * D * f);
-    L.rel_repr = take((size_t)(L.dedupe ? R : e1) * D * f);
-    L.rel_rows = take(L.dedupe ? (size_t)R * D * f : 256);
-    L.rel_first = take(L.dedupe ? (size_t)R * 4 : 256);
-    L.status = take(256);
-    L.ns = take(n1 * (F / 2) * f);
-    L.in_ptr = take((size_t)(N + 1) * 4);
-    L.in_nbr = take(e1 * 4);
-    L.in_eid = take(e1 * 4);
-    L.out_ptr = take((size_t)(N + 1) * 4);
-    L.out_nbr = take(e1 * 4);
-    L.out_eid = take(e1 * 4);
-    L.csr_ws = take(evi_graph_csr_workspace_bytes(N));
-    L.wa = take((size_t)H * D * f);
-    L.wb = take((size_t)H * D * f);
-    L.wc = take((size_t)H * D * f);
-    L.wd = take((size_t)H * f);
-    L.vhead = take((size_t)(H + 1) * f);
-    L.fold = take((size_t)32 * H * f);  // kFoldSlices partial rows of the folded head
-    L.wt = take((size_t)F * D * f);
-    L.wsplit = take(gemm_bf16x3_workspace_bytes(H > D ? H : D, H > D ? H : D));
-    L.hcn = take(n1 * H * f);
-    L.P = take((size_t)L.ec * D * f);
-    L.RCX = take((size_t)L.ec * D * f);
-    L.XS = take((size_t)dirs * L.ec * D * f);
-    L.aux = take((size_t)dirs * L.ec * 2 * f);
-    L.PA = take((size_t)L.ec * H * f);
-    L.RC = take((size_t)L.ec * H * f);
-    L.SB = take((size_t)dirs * L.ec * H * f);
-    L.h1n = take((size_t)L.ec * H * f);  // combined normalised rows (input of state_net.4 when features are wanted)
+    L.rel_first = m.take(L.dedupe ? (size_t)R * 4 : 256);
+    L.status = m.take(256);
+    L.csr_ws = m.take(evi_graph_csr_workspace_bytes(N));
+    L.wts = place_weight_derived(m, D, H, F);
+    L.wsplit = m.take(gemm_bf16x3_workspace_bytes(H > D ? H : D, H > D ? H : D));
+    L.P = m.take((size_t)L.ec * D * f);
+    L.RCX = m.take((size_t)L.ec * D * f);
+    L.XS = m.take((size_t)dirs * L.ec * D * f);
+    L.aux = m.take((size_t)dirs * L.ec * 2 * f);
+    L.PA = m.take((size_t)L.ec * H * f);
+    L.RC = m.take((size_t)L.ec * H * f);
+    L.SB = m.take((size_t)dirs * L.ec * H * f);
+    L.h1n = m.take((size_t)L.ec * H * f);  // combined normalised rows (input of state_net.4 when features are wanted)
     const int64_t table = (int64_t)B * R;
     L.pair_max = (L.dedupe && scorer_pairs() && !use_f32_gemm() && table <= kPairTableMax && E >= 1024) ? (E < table ? E : table) : 0;
-    L.pair_table = take(L.pair_max ? (size_t)table * 4 : 256);
-    L.pair_count = take(L.pair_max ? (size_t)(B + 1) * 4 : 256);
-    L.pair_key = take(L.pair_max ? (size_t)L.pair_max * 4 : 256);
-    L.pair_rcx = take(L.pair_max ? (size_t)L.pair_max * D * f : 256);
-    L.pair_rc = take(L.pair_max ? (size_t)L.pair_max * H * f : 256);
-    L.total = off;
+    L.pair_table = m.take(L.pair_max ? (size_t)table * 4 : 256);
+    L.pair_count = m.take(L.pair_max ? (size_t)(B + 1) * 4 : 256);
+    L.pair_key = m.take(L.pair_max ? (size_t)L.pair_max * 4 : 256);
+    L.pair_rcx = m.take(L.pair_max ? (size_t)L.pair_max * D * f : 256);
+    L.pair_rc = m.take(L.pair_max ? (size_t)L.pair_max * H * f : 256);
+    L.total = m.total;
     return L;
+}
+
+template <typename T = float>
+static T* at_offset(const void* base, size_t off) {
+    return reinterpret_cast<T*>(static_cast<char*>(const_cast<void*>(base)) + off);
+}
+
+// A section's pointers, resolved once against the buffer that holds it
+struct WeightPtrs {
+    float *wa, *wb, *wc, *wd, *wt, *vhead, *fold;
+};
+static WeightPtrs weight_ptrs(const void* base, const WeightDerived& W) {
+    return {at_offset(base, W.wa), at_offset(base, W.wb), at_offset(base, W.wc), at_offset(base, W.wd),
+            at_offset(base, W.wt), at_offset(base, W.vhead), at_offset(base, W.fold)};
+}
+
+struct NodePtrs {
+    float *node_repr, *non_text, *q_proj, *gate_q, *bias_q, *rel_repr, *rel_rows, *ns, *hcn;
+    int32_t *in_ptr, *in_nbr, *in_eid, *out_ptr, *out_nbr, *out_eid;
+};
+static NodePtrs node_ptrs(void* base, const NodeKeep& K) {
+    return {at_offset(base, K.node_repr), at_offset(base, K.non_text), at_offset(base, K.q_proj), at_offset(base, K.gate_q),
+            at_offset(base, K.bias_q), at_offset(base, K.rel_repr), at_offset(base, K.rel_rows), at_offset(base, K.ns),
+            at_offset(base, K.hcn), at_offset<int32_t>(base, K.in_ptr), at_offset<int32_t>(base, K.in_nbr),
+            at_offset<int32_t>(base, K.in_eid), at_offset<int32_t>(base, K.out_ptr), at_offset<int32_t>(base, K.out_nbr),
+            at_offset<int32_t>(base, K.out_eid)};
+}
+
+// the prepared bf16 hi / lo planes of the GEMM weights; all null without a prepared buffer (scorer_gemm splits the weight)
+struct PlanePtrs {
+    const void *entity, *query, *gate, *bias, *rel, *wa, *wb, *wc, *s4;
+};
+static PlanePtrs plane_ptrs(const char* prep, const PrepLayout& P) {
+    if (!prep) return {};
+    return {prep + P.p_entity, prep + P.p_query, prep + P.p_gate, prep + P.p_bias, prep + P.p_rel,
+            prep + P.p_wa, prep + P.p_wb, prep + P.p_wc, prep + P.p_s4};
+}
+
+// The f32 section of the weight-derived pieces: the column blocks of state_net.0, the transposed struct_proj weight and the
+// folded head v = W2^T w, v[H] = w . b2 + b.  Made by evi_retriever_prepare, and by every forward without a prepared buffer.
+static int derive_weights(const EviRetrieverWeights* w, int D, int H, int F, const WeightPtrs& p, hipStream_t st) {
+    hipLaunchKernelGGL(k_slice_state0, dim3(H), dim3(256), 0, st, w->state0_w, H, D, p.wa, p.wb, p.wc, p.wd);
+    hipLaunchKernelGGL(k_transpose, dim3((F * D + 255) / 256), dim3(256), 0, st, w->struct_w, D, F, p.wt);
+    hipLaunchKernelGGL(k_fold_head_partial, dim3((H + 255) / 256, kFoldSlices), dim3(256), 0, st, w->state4_w, w->score_w, H,
+                       p.fold);
+    hipLaunchKernelGGL(k_fold_head_final, dim3((H + 255) / 256), dim3(256), 0, st, p.fold, w->state4_b, w->score_w,
+                       w->score_b, H, p.vhead);
+    EVI_LAUNCH_CHECK();
+    return EVI_OK;
 }
 
 }  // namespace evi
@@ -777,23 +839,17 @@ extern "C" int evi_retriever_prepare(const EviRetrieverWeights* w, void* prepare
         return fail(EVI_ERR_NOMEM, "evi_retriever_prepare: buffer %zu B < %zu B", prepared_bytes, PL.total);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* base = static_cast<char*>(prepared);
-    auto PF = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
-    hipLaunchKernelGGL(k_slice_state0, dim3(H), dim3(256), 0, st, w->state0_w, H, D, PF(PL.wa), PF(PL.wb), PF(PL.wc), PF(PL.wd));
-    hipLaunchKernelGGL(k_transpose, dim3((F * D + 255) / 256), dim3(256), 0, st, w->struct_w, D, F, PF(PL.wt));
-    hipLaunchKernelGGL(k_fold_head_partial, dim3((H + 255) / 256, kFoldSlices), dim3(256), 0, st, w->state4_w, w->score_w, H,
-                       PF(PL.fold));
-    hipLaunchKernelGGL(k_fold_head_final, dim3((H + 255) / 256), dim3(256), 0, st, PF(PL.fold), w->state4_b, w->score_w,
-                       w->score_b, H, PF(PL.vhead));
-    EVI_LAUNCH_CHECK();
+    const WeightPtrs p = weight_ptrs(base, PL.wts);
     int rc;
+    if ((rc = derive_weights(w, D, H, F, p, st))) return rc;
     if ((rc = split_weight_bf16x3(w->entity_w, D, D, D, base + PL.p_entity, st))) return rc;
     if ((rc = split_weight_bf16x3(w->query_w, D, D, D, base + PL.p_query, st))) return rc;
     if ((rc = split_weight_bf16x3(w->q_gate_w, D, D, D, base + PL.p_gate, st))) return rc;
     if ((rc = split_weight_bf16x3(w->q_bias_w, D, D, D, base + PL.p_bias, st))) return rc;
     if ((rc = split_weight_bf16x3(w->relation_w, D, D, D, base + PL.p_rel, st))) return rc;
-    if ((rc = split_weight_bf16x3(PF(PL.wa), H, D, D, base + PL.p_wa, st))) return rc;
-    if ((rc = split_weight_bf16x3(PF(PL.wb), H, D, D, base + PL.p_wb, st))) return rc;
-    if ((rc = split_weight_bf16x3(PF(PL.wc), H, D, D, base + PL.p_wc, st))) return rc;
+    if ((rc = split_weight_bf16x3(p.wa, H, D, D, base + PL.p_wa, st))) return rc;
+    if ((rc = split_weight_bf16x3(p.wb, H, D, D, base + PL.p_wb, st))) return rc;
+    if ((rc = split_weight_bf16x3(p.wc, H, D, D, base + PL.p_wc, st))) return rc;
     if ((rc = split_weight_bf16x3(w->state4_w, H, H, H, base + PL.p_s4, st))) return rc;
     return EVI_OK;
 }
@@ -804,53 +860,6 @@ extern "C" size_t evi_retriever_forward_workspace_bytes(int64_t N, int64_t E, in
     const int F = 2 * 2 * (1 + dde_rounds + dde_reverse_rounds);
     return fwd_layout(N, E, B, D, H, F, num_relations, 2).total;
 }
-
-// The node-level results of a training forward, kept behind the per-edge rows of `saved` when the caller's buffer has room
-// (evi_retriever_saved_bytes_full): projected nodes / questions / relations, the structure features, both CSR halves and
-// node_repr Wc^T.  The backward then starts from them instead of recomputing the node-level forward (three large GEMMs, the CSR
-// build, DDE, the relation de-duplication: ~0.6 ms of a 13.6 ms step at the bench shape).
-struct NodeKeep {
-    size_t node_repr, non_text, q_proj, gate_q, bias_q, rel_repr, rel_rows, ns, in_ptr, in_nbr, in_eid, out_ptr, out_nbr, out_eid, hcn, total;
-};
-static NodeKeep node_keep_layout(int64_t N, int64_t E, int B, int D, int H, int F, int64_t R, int dedupe) {
-    NodeKeep K;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
-    const size_t f = sizeof(float);
-    const size_t n1 = (size_t)(N > 0 ? N : 1), e1 = (size_t)(E > 0 ? E : 1);
-    K.node_repr = take(n1 * D * f);
-    K.non_text = take((size_t)D * f);
-    K.q_proj = take((size_t)B * D * f);
-    K.gate_q = take((size_t)B * D * f);
-    K.bias_q = take((size_t)B * D * f);
-    K.rel_repr = take((size_t)(dedupe ? R : e1) * D * f);
-    K.rel_rows = take(dedupe ? (size_t)R * D * f : 256);
-    K.ns = take(n1 * (F / 2) * f);
-    K.in_ptr = take((size_t)(N + 1) * 4);
-    K.in_nbr = take(e1 * 4);
-    K.in_eid = take(e1 * 4);
-    K.out_ptr = take((size_t)(N + 1) * 4);
-    K.out_nbr = take(e1 * 4);
-    K.out_eid = take(e1 * 4);
-    K.hcn = take(n1 * H * f);
-    K.total = off;
-    return K;
-}
-
-// Backward context of retriever_run (null: forward only).  Gradients use the weights struct's layout (float* written).
-struct BwdCtx {
-    const float* dlogits;          // [E]
-    const EviRetrieverWeights* g;  // gradient buffers, same shapes as the weights
-    const int64_t* rel_perm;       // [E] edge ids grouped by relation id (stable), or null when relations are not de-duplicated
-    const int64_t* rel_ptr;        // [R + 1] segment bounds into rel_perm
-    char* ws;                      // backward workspace (evi_retriever_backward_workspace_bytes)
-    const char* saved;             // the forward's per-edge intermediates (EviRetrieverOutput.saved), or null: recompute them
-    size_t saved_bytes;
-};
 
 struct BwdLayout {
     size_t DZ, DPA, DRC, daux, dP, dRCX, dXS, DU, SX, partC, partE, DDF, DH, DT, DRR, DGQ, DBQ, dNR, dHcN, tmpN, dRRu, dGQ, dBQ, dQP,
@@ -863,12 +872,7 @@ constexpr int kTnMaxSlices = 64;
 
 static BwdLayout bwd_layout(int64_t N, int64_t E, int B, int D, int H, int F, int64_t R, int64_t ec) {
     BwdLayout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t at = off;
-        off = align_up(off + bytes, 256);
-        return at;
-    };
+    Bump m;
     const size_t f = sizeof(float);
     const int mx = D > H ? D : H;
     const size_t e1 = (size_t)(E > 0 ? E : 1), n1 = (size_t)(N > 0 ? N : 1);
@@ -877,43 +881,43 @@ static BwdLayout bwd_layout(int64_t N, int64_t E, int B, int D, int H, int F, in
     L.wavesE = 6;  // 384-thread workgroups: ~150 registers per lane and (F + 4) D floats of LDS -> two workgroups, 12 waves per CU
     L.gridE = (int)((ec + L.wavesE - 1) / L.wavesE < 1024 ? (ec + L.wavesE - 1) / L.wavesE : 1024);
     if (L.gridE < 1) L.gridE = 1;
-    L.DZ = take((size_t)2 * ec * H * f);
-    L.DPA = take((size_t)ec * H * f);
-    L.DRC = take((size_t)ec * H * f);
-    L.daux = take((size_t)2 * ec * 2 * f);
-    L.dP = take((size_t)ec * D * f);
-    L.dRCX = take((size_t)ec * D * f);
-    L.dXS = take((size_t)2 * ec * D * f);
-    L.DU = take((size_t)2 * ec * D * f);
-    L.SX = take((size_t)2 * ec * F * f);
-    L.partC = take(((size_t)L.gridC * 5 * H + L.gridC) * f);
-    L.partE = take(((size_t)L.gridE * L.wavesE * 4 * D + (size_t)L.gridE * L.wavesE) * f);
-    L.DDF = take(e1 * H * f);
-    L.DH = take(e1 * D * f);
-    L.DT = take(e1 * D * f);
-    L.DRR = take(e1 * D * f);
-    L.DGQ = take(e1 * D * f);
-    L.DBQ = take(e1 * D * f);
-    L.dNR = take(n1 * D * f);
-    L.dHcN = take(n1 * H * f);
-    L.tmpN = take(n1 * D * f);
-    L.dRRu = take((size_t)(R > 0 ? R : 1) * D * f);
-    L.dGQ = take((size_t)B * D * f);
-    L.dBQ = take((size_t)B * D * f);
-    L.dQP = take((size_t)B * D * f * 2);
-    L.dnt = take((size_t)D * f * 2);
-    L.WaT = take((size_t)D * H * f);
-    L.WbT = take((size_t)D * H * f);
-    L.WcT = take((size_t)D * H * f);
-    L.WgT = take((size_t)D * D * f);
-    L.WbqT = take((size_t)D * D * f);
-    L.WeT = take((size_t)D * D * f);
-    L.gWa = take((size_t)H * D * f);
-    L.gWb = take((size_t)H * D * f);
-    L.gWc = take((size_t)H * D * f);
-    L.gwd = take((size_t)H * f);
-    L.ysum = take((size_t)H * f);
-    L.ssum = take(256);
+    L.DZ = m.take((size_t)2 * ec * H * f);
+    L.DPA = m.take((size_t)ec * H * f);
+    L.DRC = m.take((size_t)ec * H * f);
+    L.daux = m.take((size_t)2 * ec * 2 * f);
+    L.dP = m.take((size_t)ec * D * f);
+    L.dRCX = m.take((size_t)ec * D * f);
+    L.dXS = m.take((size_t)2 * ec * D * f);
+    L.DU = m.take((size_t)2 * ec * D * f);
+    L.SX = m.take((size_t)2 * ec * F * f);
+    L.partC = m.take(((size_t)L.gridC * 5 * H + L.gridC) * f);
+    L.partE = m.take(((size_t)L.gridE * L.wavesE * 4 * D + (size_t)L.gridE * L.wavesE) * f);
+    L.DDF = m.take(e1 * H * f);
+    L.DH = m.take(e1 * D * f);
+    L.DT = m.take(e1 * D * f);
+    L.DRR = m.take(e1 * D * f);
+    L.DGQ = m.take(e1 * D * f);
+    L.DBQ = m.take(e1 * D * f);
+    L.dNR = m.take(n1 * D * f);
+    L.dHcN = m.take(n1 * H * f);
+    L.tmpN = m.take(n1 * D * f);
+    L.dRRu = m.take((size_t)(R > 0 ? R : 1) * D * f);
+    L.dGQ = m.take((size_t)B * D * f);
+    L.dBQ = m.take((size_t)B * D * f);
+    L.dQP = m.take((size_t)B * D * f * 2);
+    L.dnt = m.take((size_t)D * f * 2);
+    L.WaT = m.take((size_t)D * H * f);
+    L.WbT = m.take((size_t)D * H * f);
+    L.WcT = m.take((size_t)D * H * f);
+    L.WgT = m.take((size_t)D * D * f);
+    L.WbqT = m.take((size_t)D * D * f);
+    L.WeT = m.take((size_t)D * D * f);
+    L.gWa = m.take((size_t)H * D * f);
+    L.gWb = m.take((size_t)H * D * f);
+    L.gWc = m.take((size_t)H * D * f);
+    L.gwd = m.take((size_t)H * f);
+    L.ysum = m.take((size_t)H * f);
+    L.ssum = m.take(256);
     int64_t kmax = 2 * ec;
     if ((int64_t)N > kmax) kmax = N;
     if (E > kmax && R <= 0) kmax = E;
@@ -921,14 +925,27 @@ static BwdLayout bwd_layout(int64_t N, int64_t E, int B, int D, int H, int F, in
     if (B > kmax) kmax = B;
     kmax = (kmax + 31) / 32 * 32;
     L.kmax = kmax;
-    L.At = take((size_t)mx * kmax * f);
-    L.Bt = take((size_t)mx * kmax * f);
-    L.tnpart = take((size_t)kTnMaxSlices * mx * (mx > F ? mx : F) * f);  // slice partials [S][M][N]: M, N <= max(D, H, F)
-    L.wsplit2 = take(gemm_bf16x3_workspace_bytes(mx, (int)kmax));  // planes of a whole transposed operand (split-K batch)
-    L.colpart = take(((size_t)(kmax + kColsumRows - 1) / kColsumRows + 16) * 5 * mx * f);  // also the scratch row of the five / three column vectors
-    L.total = off;
+    L.At = m.take((size_t)mx * kmax * f);
+    L.Bt = m.take((size_t)mx * kmax * f);
+    L.tnpart = m.take((size_t)kTnMaxSlices * mx * (mx > F ? mx : F) * f);  // slice partials [S][M][N]: M, N <= max(D, H, F)
+    L.wsplit2 = m.take(gemm_bf16x3_workspace_bytes(mx, (int)kmax));  // planes of a whole transposed operand (split-K batch)
+    L.colpart = m.take(((size_t)(kmax + kColsumRows - 1) / kColsumRows + 16) * 5 * mx * f);  // also the scratch row of the five / three column vectors
+    L.total = m.total;
     return L;
 }
+
+// Backward context of retriever_run (null: forward only).  Gradients use the weights struct's layout (float* written).
+struct BwdCtx {
+    const float* dlogits;          // [E]
+    const EviRetrieverWeights* g;  // gradient buffers, same shapes as the weights
+    const int64_t* rel_perm;       // [E] edge ids grouped by relation id (stable), or null when relations are not de-duplicated
+    const int64_t* rel_ptr;        // [R + 1] segment bounds into rel_perm
+    char* ws;                      // backward workspace (evi_retriever_backward_workspace_bytes)
+    const char* saved;             // the forward's per-edge intermediates (EviRetrieverOutput.saved), or null: recompute them
+    size_t saved_bytes;
+    FwdLayout L;                   // the layouts of the forward and the backward workspace
+    BwdLayout BL;
+};
 
 // C [M, N] (+)= A^T B with A [K, M], B [K, N] row-major and K large: split-K launches of the TN kernel (gemm_tn.hip) and an
 // ordered reduction of the slice results (deterministic).  The exact-f32 mode of the tests transposes both operands and goes
@@ -1081,13 +1098,48 @@ __global__ void k_merge_state0(const float* __restrict__ ga, const float* __rest
 // SB [dirs ec, H], aux [dirs ec, 2] — the chunk workspace's own layout, kept for all chunks.
 static inline size_t saved_floats_per_edge(int D, int H, int dirs) { return (size_t)(2 + dirs) * D + (size_t)(2 + dirs) * H + 2 * (size_t)dirs; }
 
-static int retriever_run(const EviRetrieverWeights* w, const EviRetrieverBatch* b, int direction_mode,
-                         const EviRetrieverOutput* out, void* workspace, size_t workspace_bytes, void* stream,
-                         const BwdCtx* bw) {
+// One call of retriever_run: its inputs, layouts and the pointers every stage reads, resolved once (validate, resolve)
+struct Run {
+    const EviRetrieverWeights* w;
+    const EviRetrieverBatch* b;
+    const EviRetrieverOutput* out;
+    const BwdCtx* bw;  // null: forward only
+    void* stream;
+    hipStream_t st;
+    int64_t N, E;
+    int B, D, H, F, dir_fwd, dir_bwd, dirs, dpl_d, dpl_h;
+    uint32_t drop_thr;
+    FwdLayout L;
+    BwdLayout BL;
+    char* base;   // forward workspace
+    char* bws;    // backward workspace
+    void* wsplit;
+    NodePtrs n;       // node-level results: in the workspace, or in `saved` behind its per-edge rows
+    WeightPtrs wts;   // weight-derived pieces: in the caller's prepared buffer, or in the workspace
+    PlanePtrs planes;
+    float* saved;     // training: the per-edge intermediates, written by the forward and replayed by the backward
+    bool prep;            // the weight-derived pieces come prepared
+    bool nodes_kept;      // the node-level results live in `saved`
+    bool nodes_replayed;  // ... and this is the backward of that forward: the node-level forward is skipped
+    bool replay;          // the backward replays the per-edge rows of `saved`: the per-chunk forward is skipped
+    bool pairs;           // r_ctx Wc^T once per (relation, graph) pair (forward-only calls)
+    bool table_given;     // the relation table was handed over (relation_rows)
+    float* ws(size_t off) const { return at_offset(base, off); }
+    int32_t* wsi(size_t off) const { return at_offset<int32_t>(base, off); }
+    float* bf(size_t off) const { return at_offset(bws, off); }
+};
+static float* grad(const float* p) { return const_cast<float*>(p); }  // gradient buffers live in a weights-shaped struct
+
+static int validate(Run& r, const EviRetrieverWeights* w, const EviRetrieverBatch* b, int direction_mode,
+                    const EviRetrieverOutput* out, void* workspace, size_t workspace_bytes, const BwdCtx* bw) {
     EVI_REQUIRE(w && b && out, "evi_retriever_forward: null struct pointer");
-    const int D = w->emb_dim, H = w->hidden_dim;
-    const int64_t N = b->num_nodes, E = b->num_edges;
-    const int B = b->num_graphs;
+    r.w = w;
+    r.b = b;
+    r.out = out;
+    r.bw = bw;
+    const int D = r.D = w->emb_dim, H = r.H = w->hidden_dim;
+    const int64_t N = r.N = b->num_nodes, E = r.E = b->num_edges;
+    const int B = r.B = b->num_graphs;
     EVI_REQUIRE(D >= 1 && H >= 1, "evi_retriever_forward: bad dims emb_dim=%d hidden_dim=%d", D, H);
     if (D % 4 != 0 || H % 4 != 0 || D > 1280 || H > 1280)
         return fail(EVI_ERR_UNSUPPORTED, "evi_retriever_forward: emb_dim/hidden_dim must be multiples of 4 and <= 1280, got %d/%d", D, H);
@@ -1110,127 +1162,130 @@ static int retriever_run(const EviRetrieverWeights* w, const EviRetrieverBatch* 
     EVI_REQUIRE(b->topic_stride >= 2, "topic_one_hot feature dim %d < num_topics=2", b->topic_stride);
     EVI_REQUIRE(b->node_ptr && b->edge_ptr && b->edge_batch, "evi_retriever_forward: node_ptr/edge_ptr/edge_batch required");
     EVI_REQUIRE(out->logits, "evi_retriever_forward: output logits pointer is null");
-    const int dir_fwd = direction_mode != 2, dir_bwd = direction_mode != 1;
-    const int dirs = dir_fwd + dir_bwd;
+    r.dir_fwd = direction_mode != 2;
+    r.dir_bwd = direction_mode != 1;
+    r.dirs = r.dir_fwd + r.dir_bwd;
     EVI_REQUIRE(b->dropout_p >= 0.f && b->dropout_p < 1.f, "dropout probability has to be between 0 and 1, but got %g", (double)b->dropout_p);
-    uint32_t drop_thr = (uint32_t)lrintf(b->dropout_p * 65536.0f);
-    if (drop_thr > 65535u) drop_thr = 65535u;
+    r.drop_thr = (uint32_t)lrintf(b->dropout_p * 65536.0f);
+    if (r.drop_thr > 65535u) r.drop_thr = 65535u;
     EVI_REQUIRE(b->matmul_precision >= 0 && b->matmul_precision <= 2,
                 "matmul_precision must be 0 (split-bf16, three products), 1 (one bf16 product) or 2 (f16x2: two f16 products, forward only), got %d",
                 b->matmul_precision);
     EVI_REQUIRE(!(b->matmul_precision == 2 && bw), "matmul_precision 2 (f16x2) is an evaluation-time option: the backward runs with 0 or 1");
-    const SingleProductScope precision_scope(b->matmul_precision);
-    const int S = 1 + w->dde_rounds + w->dde_reverse_rounds;
-    const int F = 2 * 2 * S;
-    const FwdLayout L = fwd_layout(N, E, B, D, H, F, b->num_relations, 2);
+    const int F = r.F = 2 * 2 * (1 + w->dde_rounds + w->dde_reverse_rounds);
+    r.L = bw ? bw->L : fwd_layout(N, E, B, D, H, F, b->num_relations, 2);
     EVI_REQUIRE(workspace, "evi_retriever_forward: null workspace");
-    if (workspace_bytes < L.total)
-        return fail(EVI_ERR_NOMEM, "evi_retriever_forward: workspace %zu B < %zu B", workspace_bytes, L.total);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char* base = static_cast<char*>(workspace);
-    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
-    auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(base + off); };
+    if (workspace_bytes < r.L.total)
+        return fail(EVI_ERR_NOMEM, "evi_retriever_forward: workspace %zu B < %zu B", workspace_bytes, r.L.total);
+    const void* saved = bw ? static_cast<const void*>(bw->saved) : out->saved;
+    if (saved) {
+        const size_t need = (size_t)E * saved_floats_per_edge(D, H, r.dirs) * sizeof(float);
+        const size_t have = bw ? bw->saved_bytes : out->saved_bytes;
+        if (have < need) return fail(EVI_ERR_NOMEM, "evi_retriever: saved buffer %zu B < %zu B", have, need);
+    }
+    return EVI_OK;
+}
+
+// Where each section lives and which stages run: the mode flags, the section pointers
+static void resolve(Run& r, void* workspace, void* stream) {
+    const EviRetrieverWeights* w = r.w;
+    const EviRetrieverBatch* b = r.b;
+    const EviRetrieverOutput* out = r.out;
+    const BwdCtx* bw = r.bw;
+    r.stream = stream;
+    r.st = reinterpret_cast<hipStream_t>(stream);
+    r.dpl_d = dpl_for(r.D);
+    r.dpl_h = dpl_for(r.H);
+    r.base = static_cast<char*>(workspace);
+    r.wsplit = r.base + r.L.wsplit;
+    // training: the forward writes its per-edge intermediates into the caller's `saved` buffer and the backward replays them
+    // instead of recomputing the per-edge forward (edge features, three GEMMs, the combine)
+    char* sv = bw ? const_cast<char*>(bw->saved) : static_cast<char*>(out->saved);
+    const size_t have = bw ? bw->saved_bytes : out->saved_bytes;
+    r.saved = reinterpret_cast<float*>(sv);
+    r.replay = bw && bw->saved;
     // node-level results: in the workspace, or — training, when `saved` has room behind its per-edge rows — in `saved`, where the
     // backward of the same step finds them (nodes_replayed) instead of recomputing
-    const size_t edge_saved_bytes = align_up((size_t)E * saved_floats_per_edge(D, H, dirs) * sizeof(float), 256);
-    const NodeKeep NK = node_keep_layout(N, E, B, D, H, F, b->num_relations, L.dedupe);
-    char* nkeep = nullptr;
-    {
-        char* sv = bw ? const_cast<char*>(bw->saved) : static_cast<char*>(out->saved);
-        const size_t have = bw ? bw->saved_bytes : out->saved_bytes;
-        if (sv && have >= edge_saved_bytes + NK.total) nkeep = sv + edge_saved_bytes;
-    }
-    const bool nodes_replayed = bw && nkeep;
-    auto NF = [&](size_t ws_off, size_t keep_off) { return reinterpret_cast<float*>(nkeep ? nkeep + keep_off : base + ws_off); };
-    auto NI = [&](size_t ws_off, size_t keep_off) { return reinterpret_cast<int32_t*>(nkeep ? nkeep + keep_off : base + ws_off); };
-    float* node_repr = NF(L.node_repr, NK.node_repr);
-    float* non_text = NF(L.non_text, NK.non_text);
-    float* q_proj = NF(L.q_proj, NK.q_proj);
-    float* gate_q = NF(L.gate_q, NK.gate_q);
-    float* bias_q = NF(L.bias_q, NK.bias_q);
-    float* rel_repr = NF(L.rel_repr, NK.rel_repr);
+    const size_t edge_saved_bytes = align_up((size_t)r.E * saved_floats_per_edge(r.D, r.H, r.dirs) * sizeof(float), 256);
+    r.nodes_kept = sv && have >= edge_saved_bytes + r.L.node.total;
+    r.nodes_replayed = bw && r.nodes_kept;
+    r.n = node_ptrs(r.nodes_kept ? sv + edge_saved_bytes : r.base, r.L.node);
     // the relation table handed over (relation_rows): its rows ARE the de-duplicated relation rows, nothing is gathered or kept
-    const bool table_given = L.dedupe && b->relation_rows;
-    float* rel_rows = table_given ? const_cast<float*>(b->relation_rows) : NF(L.rel_rows, NK.rel_rows);
-    float* ns = nkeep ? NF(0, NK.ns) : (out->node_struct ? out->node_struct : F32(L.ns));
-    int32_t *in_ptr = NI(L.in_ptr, NK.in_ptr), *in_nbr = NI(L.in_nbr, NK.in_nbr), *in_eid = NI(L.in_eid, NK.in_eid);
-    int32_t *out_ptr = NI(L.out_ptr, NK.out_ptr), *out_nbr = NI(L.out_nbr, NK.out_nbr), *out_eid = NI(L.out_eid, NK.out_eid);
-    void* wsplit = base + L.wsplit;
-    int rc;
-    // weight-derived pieces: from the caller's prepared buffer when it keeps one, else made below in the workspace
+    r.table_given = r.L.dedupe && b->relation_rows;
+    if (r.table_given) r.n.rel_rows = const_cast<float*>(b->relation_rows);
+    if (!r.nodes_kept && out->node_struct) r.n.ns = out->node_struct;
+    // weight-derived pieces: from the caller's prepared buffer when it keeps one, else made in the workspace
     const char* prep = static_cast<const char*>(w->prepared);
-    const PrepLayout PL = prep_layout(D, H, F);
-    auto planes = [&](size_t off) -> const void* { return prep ? prep + off : nullptr; };
+    const PrepLayout PL = prep_layout(r.D, r.H, r.F);
+    r.prep = prep != nullptr;
+    r.wts = prep ? weight_ptrs(prep, PL.wts) : weight_ptrs(r.base, r.L.wts);
+    r.planes = plane_ptrs(prep, PL);
+    // the backward and the saved-activation forward keep per-edge rows
+    r.pairs = r.L.pair_max > 0 && !bw && !r.saved;
+    if (bw) {
+        r.BL = bw->BL;
+        r.bws = bw->ws;
+    }
+}
 
-    if (!nodes_replayed) {  // (the backward of a step whose forward kept its node-level results skips 1 and 2)
-    // 1. projections
-    if ((rc = scorer_gemm(b->node_embeddings, N, D, D, w->entity_w, D, D, w->entity_b, 1, node_repr, D, wsplit, st, planes(PL.p_entity)))) return rc;
-    if ((rc = scorer_gemm(w->non_text_emb, 1, D, D, w->entity_w, D, D, w->entity_b, 1, non_text, D, wsplit, st, planes(PL.p_entity)))) return rc;
-    hipLaunchKernelGGL(k_overwrite_non_text, dim3((unsigned)N), dim3(256), 0, st, node_repr, b->node_embedding_ids,
-                       non_text, N, D);
+// 1. projections, 2. structure features
+static int node_forward(const Run& r) {
+    const EviRetrieverWeights* w = r.w;
+    const EviRetrieverBatch* b = r.b;
+    const NodePtrs& n = r.n;
+    const PlanePtrs& pl = r.planes;
+    const int64_t N = r.N, E = r.E;
+    const int B = r.B, D = r.D;
+    hipStream_t st = r.st;
+    int rc;
+    if ((rc = scorer_gemm(b->node_embeddings, N, D, D, w->entity_w, D, D, w->entity_b, 1, n.node_repr, D, r.wsplit, st, pl.entity))) return rc;
+    if ((rc = scorer_gemm(w->non_text_emb, 1, D, D, w->entity_w, D, D, w->entity_b, 1, n.non_text, D, r.wsplit, st, pl.entity))) return rc;
+    hipLaunchKernelGGL(k_overwrite_non_text, dim3((unsigned)N), dim3(256), 0, st, n.node_repr, b->node_embedding_ids,
+                       n.non_text, N, D);
     EVI_LAUNCH_CHECK();
-    if ((rc = scorer_gemm(b->question_emb, B, D, D, w->query_w, D, D, w->query_b, 1, q_proj, D, wsplit, st, planes(PL.p_query)))) return rc;
-    if ((rc = scorer_gemm(q_proj, B, D, D, w->q_gate_w, D, D, w->q_gate_b, 2, gate_q, D, wsplit, st, planes(PL.p_gate)))) return rc;
-    if ((rc = scorer_gemm(q_proj, B, D, D, w->q_bias_w, D, D, w->q_bias_b, 1, bias_q, D, wsplit, st, planes(PL.p_bias)))) return rc;
-    if (L.dedupe) {
+    if ((rc = scorer_gemm(b->question_emb, B, D, D, w->query_w, D, D, w->query_b, 1, n.q_proj, D, r.wsplit, st, pl.query))) return rc;
+    if ((rc = scorer_gemm(n.q_proj, B, D, D, w->q_gate_w, D, D, w->q_gate_b, 2, n.gate_q, D, r.wsplit, st, pl.gate))) return rc;
+    if ((rc = scorer_gemm(n.q_proj, B, D, D, w->q_bias_w, D, D, w->q_bias_b, 1, n.bias_q, D, r.wsplit, st, pl.bias))) return rc;
+    if (r.L.dedupe) {
         const int64_t R = b->num_relations;
-        int32_t* first = I32(L.rel_first);
+        int32_t* first = r.wsi(r.L.rel_first);
         // out-of-range relation ids: OR-ed into the caller's sticky status word when it gave one (read once per epoch by the
         // host mirror: Retriever.check_deferred), else into a scratch word nobody reads
-        int32_t* status = out->status ? out->status : I32(L.status);
-        if (!out->status) EVI_HIP_CHECK(hipMemsetAsync(status, 0, 4, st));
-        if (table_given) {
+        int32_t* status = r.out->status ? r.out->status : r.wsi(r.L.status);
+        if (!r.out->status) EVI_HIP_CHECK(hipMemsetAsync(status, 0, 4, st));
+        if (r.table_given) {
             hipLaunchKernelGGL(k_check_relation_range, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, b->edge_attr, E, R, status);
         } else {
             hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, first, R, 0x7FFFFFFF);
             hipLaunchKernelGGL(k_first_edge_of_relation, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, b->edge_attr,
                                E, R, first, status);
             hipLaunchKernelGGL(k_gather_relation_rows, dim3((unsigned)R), dim3(256), 0, st, b->edge_embeddings, first, D,
-                               rel_rows);
+                               n.rel_rows);
         }
         EVI_LAUNCH_CHECK();
-        if ((rc = scorer_gemm(rel_rows, R, D, D, w->relation_w, D, D, w->relation_b, 1, rel_repr, D, wsplit, st, planes(PL.p_rel)))) return rc;
+        if ((rc = scorer_gemm(n.rel_rows, R, D, D, w->relation_w, D, D, w->relation_b, 1, n.rel_repr, D, r.wsplit, st, pl.rel))) return rc;
     } else {
-        if ((rc = scorer_gemm(b->edge_embeddings, E, D, D, w->relation_w, D, D, w->relation_b, 1, rel_repr, D, wsplit, st, planes(PL.p_rel)))) return rc;
+        if ((rc = scorer_gemm(b->edge_embeddings, E, D, D, w->relation_w, D, D, w->relation_b, 1, n.rel_repr, D, r.wsplit, st, pl.rel))) return rc;
     }
 
-    // 2. structure features
-    if ((rc = evi_graph_csr(b->edge_index, E, b->node_ptr, b->edge_ptr, B, N, in_ptr, in_nbr, in_eid, out_ptr, out_nbr, out_eid,
-                            base + L.csr_ws, evi_graph_csr_workspace_bytes(N), stream)))
+    if ((rc = evi_graph_csr(b->edge_index, E, b->node_ptr, b->edge_ptr, B, N, n.in_ptr, n.in_nbr, n.in_eid, n.out_ptr, n.out_nbr,
+                            n.out_eid, r.base + r.L.csr_ws, evi_graph_csr_workspace_bytes(N), r.stream)))
         return rc;
-    if ((rc = evi_dde_node_struct_graphs(b->topic_one_hot, b->topic_stride, 2, N, b->node_ptr, B, in_ptr, in_nbr, out_ptr, out_nbr,
-                                         w->dde_rounds, w->dde_reverse_rounds, ns, stream)))
+    if ((rc = evi_dde_node_struct_graphs(b->topic_one_hot, b->topic_stride, 2, N, b->node_ptr, B, n.in_ptr, n.in_nbr, n.out_ptr,
+                                         n.out_nbr, w->dde_rounds, w->dde_reverse_rounds, n.ns, r.stream)))
         return rc;
-    if (nkeep && out->node_struct)  // the caller wants the structure features as well: a copy of the kept rows
-        EVI_HIP_CHECK(hipMemcpyAsync(out->node_struct, ns, (size_t)N * (F / 2) * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
+    if (r.nodes_kept && r.out->node_struct)  // the caller wants the structure features as well: a copy of the kept rows
+        EVI_HIP_CHECK(hipMemcpyAsync(r.out->node_struct, n.ns, (size_t)N * (r.F / 2) * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return EVI_OK;
+}
 
-    // 3-5. factored state_net.0 (see the header), per edge chunk
-    auto PF = [&](size_t off) { return reinterpret_cast<float*>(const_cast<char*>(prep) + off); };
-    float *wa = prep ? PF(PL.wa) : F32(L.wa), *wb = prep ? PF(PL.wb) : F32(L.wb), *wc = prep ? PF(PL.wc) : F32(L.wc);
-    float *wd = prep ? PF(PL.wd) : F32(L.wd), *vhead = prep ? PF(PL.vhead) : F32(L.vhead), *hcn = NF(L.hcn, NK.hcn);
-    float* wt = prep ? PF(PL.wt) : F32(L.wt);
-    if (!prep) {
-        hipLaunchKernelGGL(k_slice_state0, dim3(H), dim3(256), 0, st, w->state0_w, H, D, wa, wb, wc, wd);
-        hipLaunchKernelGGL(k_transpose, dim3((F * D + 255) / 256), dim3(256), 0, st, w->struct_w, D, F, wt);
-        EVI_LAUNCH_CHECK();
-    }
-    if (!prep) {  // the folded head v = W2^T w, v[H] = w . b2 + b
-        float* partial = F32(L.fold);
-        hipLaunchKernelGGL(k_fold_head_partial, dim3((H + 255) / 256, kFoldSlices), dim3(256), 0, st, w->state4_w,
-                           w->score_w, H, partial);
-        hipLaunchKernelGGL(k_fold_head_final, dim3((H + 255) / 256), dim3(256), 0, st, partial, w->state4_b, w->score_w,
-                           w->score_b, H, vhead);
-        EVI_LAUNCH_CHECK();
-    }
-    if (!nodes_replayed && (rc = scorer_gemm(node_repr, N, D, D, wc, H, D, nullptr, 0, hcn, H, wsplit, st, planes(PL.p_wc)))) return rc;
-    const int dpl_d = dpl_for(D), dpl_h = dpl_for(H);
-    const size_t feat_lds = (size_t)(F + 4) * D * sizeof(float);
-    // ---- backward: set-up ----------------------------------------------------------------------------------------
-    BwdLayout BL{};
-    char* bws = nullptr;
-    auto G = [&](const float* p) { return const_cast<float*>(p); };  // gradient buffers live in a weights-shaped struct
-    auto BF = [&](size_t off) { return reinterpret_cast<float*>(bws + off); };
+// gradients cleared, the transposed weight blocks the backward GEMMs multiply with
+static int backward_setup(const Run& r) {
+    const EviRetrieverWeights* w = r.w;
+    const EviRetrieverWeights* g = r.bw->g;
+    const BwdLayout& BL = r.BL;
+    const int D = r.D, H = r.H, F = r.F;
+    hipStream_t st = r.st;
     ZeroTable ztab{};  // buffers to clear: collected, then cleared by ONE launch (flush_zero) before anything accumulates into them
     auto zero = [&](float* p, int64_t n) {
         if (n <= 0) return;
@@ -1250,317 +1305,364 @@ static int retriever_run(const EviRetrieverWeights* w, const EviRetrieverBatch* 
         hipLaunchKernelGGL(k_transpose_pad, dim3((unsigned)((R_ + 31) / 32), (unsigned)((C_ + 31) / 32)), dim3(256), 0, st, src,
                            (int64_t)R_, C_, (int64_t)C_, dst, (int64_t)R_);
     };
-    if (bw) {
-        BL = bwd_layout(N, E, B, D, H, F, L.dedupe ? b->num_relations : 0, L.ec);
-        bws = bw->ws;
-        const EviRetrieverWeights* g = bw->g;
-        zero(G(g->entity_w), (int64_t)D * D); zero(G(g->entity_b), D); zero(G(g->relation_w), (int64_t)D * D); zero(G(g->relation_b), D);
-        zero(G(g->query_w), (int64_t)D * D); zero(G(g->query_b), D); zero(G(g->non_text_emb), D);
-        zero(G(g->q_gate_w), (int64_t)D * D); zero(G(g->q_gate_b), D); zero(G(g->q_bias_w), (int64_t)D * D); zero(G(g->q_bias_b), D);
-        zero(G(g->struct_w), (int64_t)D * F); zero(G(g->struct_b), D); zero(G(g->struct_ln_w), D); zero(G(g->struct_ln_b), D);
-        zero(G(g->struct_gate_w), D); zero(G(g->struct_gate_b), 1);
-        zero(G(g->state0_w), (int64_t)H * (3 * D + 1)); zero(G(g->state0_b), H); zero(G(g->state_ln_w), H); zero(G(g->state_ln_b), H);
-        zero(G(g->state4_w), (int64_t)H * H); zero(G(g->state4_b), H); zero(G(g->score_w), H); zero(G(g->score_b), 1);
-        zero(BF(BL.gWa), (int64_t)H * D); zero(BF(BL.gWb), (int64_t)H * D); zero(BF(BL.gWc), (int64_t)H * D); zero(BF(BL.gwd), H);
-        zero(BF(BL.ysum), H); zero(BF(BL.ssum), 1);
-        flush_zero();
-        transpose(wa, H, D, BF(BL.WaT));
-        transpose(wb, H, D, BF(BL.WbT));
-        transpose(wc, H, D, BF(BL.WcT));
-        transpose(w->q_gate_w, D, D, BF(BL.WgT));
-        transpose(w->q_bias_w, D, D, BF(BL.WbqT));
-        transpose(w->entity_w, D, D, BF(BL.WeT));
-        EVI_LAUNCH_CHECK();
-    }
-    // training: the forward writes its per-edge intermediates into the caller's `saved` buffer and the backward replays them
-    // instead of recomputing the per-edge forward (edge features, three GEMMs, the combine)
-    float* saved = bw ? reinterpret_cast<float*>(const_cast<char*>(bw->saved)) : static_cast<float*>(out->saved);
-    const bool replay = bw && bw->saved;
-    if (saved) {
-        const size_t need = (size_t)E * saved_floats_per_edge(D, H, dirs) * sizeof(float);
-        const size_t have = bw ? bw->saved_bytes : out->saved_bytes;
-        if (have < need) return fail(EVI_ERR_NOMEM, "evi_retriever: saved buffer %zu B < %zu B", have, need);
-    }
-    // r_ctx Wc^T once per (relation, graph) pair (forward-only calls; the backward and the saved-activation forward keep per-edge rows)
-    const bool pairs = L.pair_max > 0 && !bw && !saved;
-    if (pairs) {
-        const int64_t R = b->num_relations;
-        int32_t *table = I32(L.pair_table), *count = I32(L.pair_count), *key = I32(L.pair_key);
-        EVI_HIP_CHECK(hipMemsetAsync(table, 0, (size_t)B * R * 4, st));
-        hipLaunchKernelGGL(k_pair_mark, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, b->edge_attr, b->edge_batch, E, R, table);
-        hipLaunchKernelGGL(k_pair_rank, dim3((unsigned)B), dim3(1024), 0, st, table, R, count);
-        hipLaunchKernelGGL(k_pair_slots, dim3((unsigned)B), dim3(256), 0, st, table, R, B, count, key);
-        hipLaunchKernelGGL(k_pair_rows, dim3((unsigned)((L.pair_max + 3) / 4)), dim3(256), 0, st, key, count + B, R, rel_repr, gate_q, bias_q,
-                           D, F32(L.pair_rcx));
-        EVI_LAUNCH_CHECK();
-        // always the tiled split-bf16 kernel, also for a handful of pairs: a row's result does not depend on where it sits in the
-        // product, so the pair rows equal the per-edge rows bit for bit (the exact-f32 skinny kernel would not)
-        if (prep && t_gemm_single != 2) {
-            if ((rc = launch_gemm_nt_bf16x3_wplanes(F32(L.pair_rcx), L.pair_max, D, D, planes(PL.p_wc), H, nullptr, 0, F32(L.pair_rc), H, st,
-                                                    t_gemm_single, count + B)))
-                return rc;
-        } else if ((rc = launch_gemm_nt_bf16x3(F32(L.pair_rcx), L.pair_max, D, D, wc, H, D, nullptr, 0, F32(L.pair_rc), H, wsplit, st,
-                                               t_gemm_single, count + B))) {
-            return rc;
+    zero(grad(g->entity_w), (int64_t)D * D); zero(grad(g->entity_b), D); zero(grad(g->relation_w), (int64_t)D * D); zero(grad(g->relation_b), D);
+    zero(grad(g->query_w), (int64_t)D * D); zero(grad(g->query_b), D); zero(grad(g->non_text_emb), D);
+    zero(grad(g->q_gate_w), (int64_t)D * D); zero(grad(g->q_gate_b), D); zero(grad(g->q_bias_w), (int64_t)D * D); zero(grad(g->q_bias_b), D);
+    zero(grad(g->struct_w), (int64_t)D * F); zero(grad(g->struct_b), D); zero(grad(g->struct_ln_w), D); zero(grad(g->struct_ln_b), D);
+    zero(grad(g->struct_gate_w), D); zero(grad(g->struct_gate_b), 1);
+    zero(grad(g->state0_w), (int64_t)H * (3 * D + 1)); zero(grad(g->state0_b), H); zero(grad(g->state_ln_w), H); zero(grad(g->state_ln_b), H);
+    zero(grad(g->state4_w), (int64_t)H * H); zero(grad(g->state4_b), H); zero(grad(g->score_w), H); zero(grad(g->score_b), 1);
+    zero(r.bf(BL.gWa), (int64_t)H * D); zero(r.bf(BL.gWb), (int64_t)H * D); zero(r.bf(BL.gWc), (int64_t)H * D); zero(r.bf(BL.gwd), H);
+    zero(r.bf(BL.ysum), H); zero(r.bf(BL.ssum), 1);
+    flush_zero();
+    transpose(r.wts.wa, H, D, r.bf(BL.WaT));
+    transpose(r.wts.wb, H, D, r.bf(BL.WbT));
+    transpose(r.wts.wc, H, D, r.bf(BL.WcT));
+    transpose(w->q_gate_w, D, D, r.bf(BL.WgT));
+    transpose(w->q_bias_w, D, D, r.bf(BL.WbqT));
+    transpose(w->entity_w, D, D, r.bf(BL.WeT));
+    EVI_LAUNCH_CHECK();
+    return EVI_OK;
+}
+
+// r_ctx Wc^T once per (relation, graph) pair instead of once per edge
+static int pair_rows(const Run& r) {
+    const EviRetrieverBatch* b = r.b;
+    const FwdLayout& L = r.L;
+    const int64_t R = b->num_relations, E = r.E;
+    const int B = r.B, D = r.D, H = r.H;
+    hipStream_t st = r.st;
+    int32_t *table = r.wsi(L.pair_table), *count = r.wsi(L.pair_count), *key = r.wsi(L.pair_key);
+    EVI_HIP_CHECK(hipMemsetAsync(table, 0, (size_t)B * R * 4, st));
+    hipLaunchKernelGGL(k_pair_mark, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, b->edge_attr, b->edge_batch, E, R, table);
+    hipLaunchKernelGGL(k_pair_rank, dim3((unsigned)B), dim3(1024), 0, st, table, R, count);
+    hipLaunchKernelGGL(k_pair_slots, dim3((unsigned)B), dim3(256), 0, st, table, R, B, count, key);
+    hipLaunchKernelGGL(k_pair_rows, dim3((unsigned)((L.pair_max + 3) / 4)), dim3(256), 0, st, key, count + B, R, r.n.rel_repr,
+                       r.n.gate_q, r.n.bias_q, D, r.ws(L.pair_rcx));
+    EVI_LAUNCH_CHECK();
+    // always the tiled split-bf16 kernel, also for a handful of pairs: a row's result does not depend on where it sits in the
+    // product, so the pair rows equal the per-edge rows bit for bit (the exact-f32 skinny kernel would not)
+    if (r.prep && t_gemm_single != 2)
+        return launch_gemm_nt_bf16x3_wplanes(r.ws(L.pair_rcx), L.pair_max, D, D, r.planes.wc, H, nullptr, 0, r.ws(L.pair_rc), H,
+                                             st, t_gemm_single, count + B);
+    return launch_gemm_nt_bf16x3(r.ws(L.pair_rcx), L.pair_max, D, D, r.wts.wc, H, D, nullptr, 0, r.ws(L.pair_rc), H, r.wsplit, st,
+                                 t_gemm_single, count + B);
+}
+
+// The per-edge rows of the chunk starting at edge e0: in the workspace, or (training) in `saved`, in the order of
+// saved_floats_per_edge
+struct Chunk {
+    int64_t e0, ec, M;  // M = dirs * ec
+    float *P, *RCX, *XS, *aux, *PA, *RC, *SB;
+};
+static Chunk chunk_at(const Run& r, int64_t e0) {
+    const int64_t ec = (r.E - e0) < r.L.ec ? (r.E - e0) : r.L.ec, M = (int64_t)r.dirs * ec;
+    if (!r.saved) return {e0, ec, M, r.ws(r.L.P), r.ws(r.L.RCX), r.ws(r.L.XS), r.ws(r.L.aux), r.ws(r.L.PA), r.ws(r.L.RC), r.ws(r.L.SB)};
+    float* P = r.saved + (size_t)e0 * saved_floats_per_edge(r.D, r.H, r.dirs);
+    float *RCX = P + ec * r.D, *XS = RCX + ec * r.D, *PA = XS + M * r.D, *RC = PA + ec * r.H, *SB = RC + ec * r.H, *aux = SB + M * r.H;
+    return {e0, ec, M, P, RCX, XS, aux, PA, RC, SB};
+}
+
+static EdgeFeatArgs edge_feat_args(const Run& r, const Chunk& c) {
+    const EviRetrieverWeights* w = r.w;
+    const EviRetrieverBatch* b = r.b;
+    EdgeFeatArgs a;
+    a.edge_index = b->edge_index;
+    a.E = r.E;
+    a.edge_batch = b->edge_batch;
+    a.edge_attr = b->edge_attr;
+    a.rel_by_edge = r.L.dedupe ? 0 : 1;
+    a.R = b->num_relations;
+    a.node_repr = r.n.node_repr;
+    a.rel_repr = r.n.rel_repr;
+    a.gate_q = r.n.gate_q;
+    a.bias_q = r.n.bias_q;
+    a.node_struct = r.n.ns;
+    a.F = r.F;
+    a.struct_wt = r.wts.wt;
+    a.struct_b = w->struct_b;
+    a.struct_ln_w = w->struct_ln_w;
+    a.struct_ln_b = w->struct_ln_b;
+    a.struct_gate_w = w->struct_gate_w;
+    a.struct_gate_b = w->struct_gate_b;
+    a.D = r.D;
+    a.e_begin = c.e0;
+    a.e_count = c.ec;
+    a.dir_fwd = r.dir_fwd;
+    a.dir_bwd = r.dir_bwd;
+    a.P = c.P;
+    a.RCX = r.pairs ? nullptr : c.RCX;
+    a.XS = c.XS;
+    a.aux = c.aux;
+    return a;
+}
+
+static CombineArgs combine_args(const Run& r, const Chunk& ch) {
+    const EviRetrieverWeights* w = r.w;
+    const EviRetrieverBatch* b = r.b;
+    const EviRetrieverOutput* out = r.out;
+    CombineArgs c;
+    c.edge_index = b->edge_index;
+    c.E = r.E;
+    c.e_begin = ch.e0;
+    c.e_count = ch.ec;
+    c.PA = ch.PA;
+    c.RC = r.pairs ? r.ws(r.L.pair_rc) : ch.RC;
+    c.pair_table = r.pairs ? r.wsi(r.L.pair_table) : nullptr;
+    c.edge_attr = b->edge_attr;
+    c.edge_batch = b->edge_batch;
+    c.R = b->num_relations;
+    c.SB = ch.SB;
+    c.HcN = r.n.hcn;
+    c.aux = ch.aux;
+    c.wd = r.wts.wd;
+    c.ln_w = w->state_ln_w;
+    c.ln_b = w->state_ln_b;
+    c.H = r.H;
+    c.dir_fwd = r.dir_fwd;
+    c.dir_bwd = r.dir_bwd;
+    c.h1c = out->edge_features ? r.ws(r.L.h1n) : nullptr;
+    c.v = r.wts.vhead;
+    c.edge_bias = b->edge_bias;
+    c.drop_thr = r.drop_thr;
+    c.drop_scale = r.drop_thr ? 65536.0f / (float)(65536u - r.drop_thr) : 1.0f;
+    c.drop_seed = b->dropout_seed;
+    c.logits = out->logits;
+    c.logits_fwd = out->logits_fwd;
+    c.logits_bwd = out->logits_bwd;
+    return c;
+}
+
+constexpr int kEdgeFeatThreads = 1024;
+
+// 3-5. factored state_net.0 (see the header) on one chunk: edge features, the three products, the combine into logits
+static int chunk_forward(const Run& r, const Chunk& ch) {
+    const EviRetrieverWeights* w = r.w;
+    const PlanePtrs& pl = r.planes;
+    const int D = r.D, H = r.H;
+    hipStream_t st = r.st;
+    int rc;
+    const EdgeFeatArgs a = edge_feat_args(r, ch);
+    const size_t feat_lds = (size_t)(r.F + 4) * D * sizeof(float);
+    int64_t blocks = (ch.ec + kEdgeFeatThreads / 64 - 1) / (kEdgeFeatThreads / 64);  // one edge per wave
+    if (blocks > 512) blocks = 512;   // 2 blocks per CU fit in LDS
+    const int tok = timing_begin(kTimeEdge, st);
+    EVI_DPL_DISPATCH(r.dpl_d, {
+        static thread_local bool attr = false;
+        if (!attr) {
+            EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_edge_features<DPL>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            attr = true;
         }
+        hipLaunchKernelGGL(k_edge_features<DPL>, dim3((unsigned)blocks), dim3(kEdgeFeatThreads), feat_lds, st, a);
+    });
+    timing_end(tok, st);
+    EVI_LAUNCH_CHECK();
+    // (r03: writing P / RCX / XS as bf16 hi / lo planes and multiplying them on a pre-split LDS-DMA GEMM was wired in here,
+    // bit-identical, and measured with rocprofv3 on this batch: 288.8 us per launch against 285.0 us for this kernel, the edge
+    // kernel 344 against 330 us — no gain inside the pipeline, so that kernel and its entry points were removed)
+    if ((rc = scorer_gemm(ch.P, ch.ec, D, D, r.wts.wa, H, D, nullptr, 0, ch.PA, H, r.wsplit, st, pl.wa))) return rc;
+    if (!r.pairs && (rc = scorer_gemm(ch.RCX, ch.ec, D, D, r.wts.wc, H, D, nullptr, 0, ch.RC, H, r.wsplit, st, pl.wc))) return rc;
+    if ((rc = scorer_gemm(ch.XS, ch.M, D, D, r.wts.wb, H, D, w->state0_b, 0, ch.SB, H, r.wsplit, st, pl.wb))) return rc;
+    const CombineArgs c = combine_args(r, ch);
+    const dim3 cgrid((unsigned)((ch.ec + 3) / 4));
+    if (c.h1c) {
+        EVI_DPL_DISPATCH(r.dpl_h, hipLaunchKernelGGL((k_state_combine<DPL, true>), cgrid, dim3(256), 0, st, c));
+    } else {
+        EVI_DPL_DISPATCH(r.dpl_h, hipLaunchKernelGGL((k_state_combine<DPL, false>), cgrid, dim3(256), 0, st, c));
     }
+    EVI_LAUNCH_CHECK();
+    if (r.out->edge_features)  // state_net.4 on the combined rows, straight into the caller's [E, H] output
+        if ((rc = scorer_gemm(c.h1c, ch.ec, H, H, w->state4_w, H, H, w->state4_b, 0, r.out->edge_features + ch.e0 * H, H, r.wsplit,
+                              st, pl.s4)))
+            return rc;
+    return EVI_OK;
+}
+
+// backward of one chunk (scorer_bwd.hpp): logits -> state rows -> per-edge gradients, the weight gradients of state_net.0
+// and struct_proj accumulated over the chunks
+static int chunk_backward(const Run& r, const Chunk& ch) {
+    const EviRetrieverWeights* g = r.bw->g;
+    const BwdLayout& BL = r.BL;
+    const int D = r.D, H = r.H, F = r.F;
+    const int64_t ec = ch.ec, M = ch.M;
+    hipStream_t st = r.st;
+    char* bws = r.bws;
+    int rc;
+    CombineBwdArgs cb;
+    cb.f = combine_args(r, ch);
+    cb.dlogits = r.bw->dlogits;
+    cb.DZ = r.bf(BL.DZ);
+    cb.DPA = r.bf(BL.DPA);
+    cb.DRC = r.bf(BL.DRC);
+    cb.DDF = r.bf(BL.DDF);
+    cb.daux = r.bf(BL.daux);
+    cb.part = r.bf(BL.partC);
+    EVI_DPL_DISPATCH(r.dpl_h, hipLaunchKernelGGL((k_combine_bwd<DPL>), dim3(BL.gridC), dim3(256), 0, st, cb));
+    EVI_LAUNCH_CHECK();
+    {   // column partials: [gridC][5][H] then [gridC] — reduce each of the five vectors and S (accumulating over chunks)
+        float* dst5[5] = {grad(g->state_ln_w), grad(g->state_ln_b), r.bf(BL.ysum), r.bf(BL.gwd), grad(g->state0_b)};
+        // the partial rows interleave the five vectors: one [gridC][5H] table, reduced straight into the five gradients
+        if ((rc = colsum_into_multi(r.bf(BL.partC), BL.gridC, 5, H, dst5, BL, bws, st))) return rc;
+        if ((rc = colsum_into(r.bf(BL.partC) + (int64_t)BL.gridC * 5 * H, BL.gridC, 1, r.bf(BL.ssum), 1, BL, bws, st))) return rc;
+    }
+    // d(state_net.0 inputs): dP = dPA Wa, dRCX = dRC Wc, dXS = dz Wb   (NT GEMMs against the transposed blocks)
+    if ((rc = scorer_gemm(r.bf(BL.DPA), ec, H, H, r.bf(BL.WaT), D, H, nullptr, 0, r.bf(BL.dP), D, r.wsplit, st))) return rc;
+    if ((rc = scorer_gemm(r.bf(BL.DRC), ec, H, H, r.bf(BL.WcT), D, H, nullptr, 0, r.bf(BL.dRCX), D, r.wsplit, st))) return rc;
+    if ((rc = scorer_gemm(r.bf(BL.DZ), M, H, H, r.bf(BL.WbT), D, H, nullptr, 0, r.bf(BL.dXS), D, r.wsplit, st))) return rc;
+    // weight blocks of state_net.0: dWa += dPA^T P, dWc += dRC^T RCX, dWb += dz^T XS
+    if ((rc = tn_gemm(r.bf(BL.DPA), H, ch.P, D, ec, r.bf(BL.gWa), 1, BL, bws, st))) return rc;
+    if ((rc = tn_gemm(r.bf(BL.DRC), H, ch.RCX, D, ec, r.bf(BL.gWc), 1, BL, bws, st))) return rc;
+    if ((rc = tn_gemm(r.bf(BL.DZ), H, ch.XS, D, M, r.bf(BL.gWb), 1, BL, bws, st))) return rc;
+    EdgeBwdArgs eb;
+    eb.f = edge_feat_args(r, ch);
+    eb.dP = r.bf(BL.dP);
+    eb.dRCX = r.bf(BL.dRCX);
+    eb.dXS = r.bf(BL.dXS);
+    eb.daux = r.bf(BL.daux);
+    eb.DH = r.bf(BL.DH);
+    eb.DT = r.bf(BL.DT);
+    // with a relation table the three uses of d r_ctx are formed from ONE stored array (DBQ) by k_segment_rowsum_mul
+    eb.DRR = r.L.dedupe ? nullptr : r.bf(BL.DRR);
+    eb.DGQ = r.L.dedupe ? nullptr : r.bf(BL.DGQ);
+    eb.DBQ = r.bf(BL.DBQ);
+    eb.DU = r.bf(BL.DU);
+    eb.SX = r.bf(BL.SX);
+    eb.part = r.bf(BL.partE);
+    const size_t lds = (size_t)(F + 4) * D * sizeof(float);
+    EVI_DPL_DISPATCH(r.dpl_d, {
+        static thread_local bool attr = false;
+        if (!attr) {
+            EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_edge_struct_bwd<DPL>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            attr = true;
+        }
+        hipLaunchKernelGGL(k_edge_struct_bwd<DPL>, dim3(BL.gridE), dim3(BL.wavesE * 64), lds, st, eb);
+        const unsigned gt = (unsigned)((ec + 3) / 4 < 8192 ? (ec + 3) / 4 : 8192);
+        hipLaunchKernelGGL(k_edge_translate_bwd<DPL>, dim3(gt > 0 ? gt : 1), dim3(256), 0, st, eb);
+    });
+    EVI_LAUNCH_CHECK();
+    // the per-wave partial table [gridE * waves][4 D] -> one row (two ordered stages), then into the four gradients
+    const int64_t prow = (int64_t)BL.gridE * BL.wavesE;
+    float* dst4[4] = {grad(g->struct_ln_w), grad(g->struct_ln_b), grad(g->struct_gate_w), grad(g->struct_b)};
+    if ((rc = colsum_into_multi(r.bf(BL.partE), prow, 4, D, dst4, BL, bws, st))) return rc;
+    if ((rc = colsum_into(r.bf(BL.partE) + prow * 4 * D, prow, 1, grad(g->struct_gate_b), 1, BL, bws, st))) return rc;
+    // struct_proj.0: weight [D, F] += dU^T SX (its bias gradient, the column sums of dU, came with the kernel's partials)
+    return tn_gemm(r.bf(BL.DU), D, r.bf(BL.SX), F, M, grad(g->struct_w), 1, BL, bws, st);
+}
+
+// backward, once per batch: the node-level and question-side gradients, the head
+static int batch_backward(const Run& r) {
+    const EviRetrieverWeights* w = r.w;
+    const EviRetrieverBatch* b = r.b;
+    const EviRetrieverWeights* g = r.bw->g;
+    const BwdLayout& BL = r.BL;
+    const NodePtrs& n = r.n;
+    const int64_t N = r.N, E = r.E;
+    const int B = r.B, D = r.D, H = r.H;
+    hipStream_t st = r.st;
+    char* bws = r.bws;
+    void* wsplit = r.wsplit;
+    int rc;
+    auto blocks_of = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    // nodes: gather the per-edge gradients through the CSR, add the Wc path (HcN = node_repr Wc^T)
+    hipLaunchKernelGGL(k_node_gather_grad, dim3((unsigned)((N * ((D + 255) / 256 + (H + 255) / 256) + 3) / 4)), dim3(256), 0, st, n.in_ptr,
+                       n.in_eid, n.out_ptr, n.out_eid, r.bf(BL.DH), r.bf(BL.DT), D, r.bf(BL.DDF), H, r.bf(BL.dNR), r.bf(BL.dHcN), (int64_t)N);
+    EVI_LAUNCH_CHECK();
+    if ((rc = scorer_gemm(r.bf(BL.dHcN), N, H, H, r.bf(BL.WcT), D, H, nullptr, 0, r.bf(BL.tmpN), D, wsplit, st))) return rc;
+    // dNR += the Wc path; the id-0 rows set aside for the non-text embedding (into tmpN, in place); tanh backward: one pass
+    hipLaunchKernelGGL(k_node_grad_finish, blocks_of((N * D + 3) / 4), dim3(256), 0, st, r.bf(BL.dNR), r.bf(BL.tmpN), n.node_repr,
+                       b->node_embedding_ids, N, D, r.bf(BL.tmpN));
+    if ((rc = tn_gemm(r.bf(BL.dHcN), H, n.node_repr, D, N, r.bf(BL.gWc), 1, BL, bws, st))) return rc;
+    hipLaunchKernelGGL(k_merge_state0, dim3(H), dim3(256), 0, st, r.bf(BL.gWa), r.bf(BL.gWb), r.bf(BL.gWc), r.bf(BL.gwd), H, D,
+                       grad(g->state0_w));
+    // the non-text embedding: its projection replaced every node row with embedding id 0
+    float* dnt = r.bf(BL.dnt);
+    if ((rc = colsum_into(r.bf(BL.tmpN), N, D, dnt, 0, BL, bws, st))) return rc;
+    hipLaunchKernelGGL(k_act_bwd, blocks_of(D), dim3(256), 0, st, dnt, n.non_text, (int64_t)1, D, 1, (const int64_t*)nullptr);
+    EVI_LAUNCH_CHECK();
+    if ((rc = scorer_gemm(dnt, 1, D, D, r.bf(BL.WeT), D, D, nullptr, 0, grad(g->non_text_emb), D, wsplit, st))) return rc;
+    // entity_proj: dpre = dNR (1 - NR^2), rows with id 0 dropped — done by k_node_grad_finish above
+    if ((rc = tn_gemm(r.bf(BL.dNR), D, b->node_embeddings, D, N, grad(g->entity_w), 0, BL, bws, st))) return rc;
+    if ((rc = tn_gemm(dnt, D, w->non_text_emb, D, 1, grad(g->entity_w), 1, BL, bws, st))) return rc;
+    if ((rc = colsum_into(r.bf(BL.dNR), N, D, grad(g->entity_b), 0, BL, bws, st))) return rc;
+    hipLaunchKernelGGL(k_add_inplace, blocks_of(D), dim3(256), 0, st, grad(g->entity_b), dnt, (int64_t)D);
+    // relation_proj
+    if (r.L.dedupe) {
+        const int64_t R = b->num_relations;
+        // d rel_repr[r] = sum over the edges of relation r of d r_ctx[e] * gate_q[graph(e)]
+        if ((rc = segment_rowsum_mul_into(r.bf(BL.DBQ), D, r.bw->rel_ptr, r.bw->rel_perm, R, E, nullptr, r.bf(BL.dRRu), n.gate_q,
+                                          b->edge_batch, (int64_t)B - 1, BL, bws, st)))
+            return rc;
+        hipLaunchKernelGGL(k_act_bwd, blocks_of(R * D), dim3(256), 0, st, r.bf(BL.dRRu), n.rel_repr, R, D, 1, (const int64_t*)nullptr);
+        EVI_LAUNCH_CHECK();
+        if ((rc = tn_gemm(r.bf(BL.dRRu), D, n.rel_rows, D, R, grad(g->relation_w), 0, BL, bws, st))) return rc;
+        if ((rc = colsum_into(r.bf(BL.dRRu), R, D, grad(g->relation_b), 0, BL, bws, st))) return rc;
+    } else {
+        hipLaunchKernelGGL(k_act_bwd, blocks_of(E * D), dim3(256), 0, st, r.bf(BL.DRR), n.rel_repr, E, D, 1, (const int64_t*)nullptr);
+        EVI_LAUNCH_CHECK();
+        if ((rc = tn_gemm(r.bf(BL.DRR), D, b->edge_embeddings, D, E, grad(g->relation_w), 0, BL, bws, st))) return rc;
+        if ((rc = colsum_into(r.bf(BL.DRR), E, D, grad(g->relation_b), 0, BL, bws, st))) return rc;
+    }
+    // question side: gate (sigmoid) and bias (tanh) of the projected question, then query_proj (tanh)
+    if (r.L.dedupe) {  // d bias_q[g] = sum of d r_ctx over the graph, d gate_q[g] = sum of d r_ctx * rel_repr[relation]: one pass
+        if ((rc = segment_rowsum_mul_into(r.bf(BL.DBQ), D, b->edge_ptr, nullptr, B, E, r.bf(BL.dBQ), r.bf(BL.dGQ), n.rel_repr,
+                                          b->edge_attr, b->num_relations - 1, BL, bws, st)))
+            return rc;
+    } else {
+        if ((rc = segment_rowsum_into(r.bf(BL.DGQ), D, b->edge_ptr, nullptr, B, E, r.bf(BL.dGQ), BL, bws, st))) return rc;
+        if ((rc = segment_rowsum_into(r.bf(BL.DBQ), D, b->edge_ptr, nullptr, B, E, r.bf(BL.dBQ), BL, bws, st))) return rc;
+    }
+    hipLaunchKernelGGL(k_act_bwd, blocks_of((int64_t)B * D), dim3(256), 0, st, r.bf(BL.dGQ), n.gate_q, (int64_t)B, D, 2, (const int64_t*)nullptr);
+    hipLaunchKernelGGL(k_act_bwd, blocks_of((int64_t)B * D), dim3(256), 0, st, r.bf(BL.dBQ), n.bias_q, (int64_t)B, D, 1, (const int64_t*)nullptr);
+    EVI_LAUNCH_CHECK();
+    if ((rc = tn_gemm(r.bf(BL.dGQ), D, n.q_proj, D, B, grad(g->q_gate_w), 0, BL, bws, st))) return rc;
+    if ((rc = tn_gemm(r.bf(BL.dBQ), D, n.q_proj, D, B, grad(g->q_bias_w), 0, BL, bws, st))) return rc;
+    if ((rc = colsum_into(r.bf(BL.dGQ), B, D, grad(g->q_gate_b), 0, BL, bws, st))) return rc;
+    if ((rc = colsum_into(r.bf(BL.dBQ), B, D, grad(g->q_bias_b), 0, BL, bws, st))) return rc;
+    float* dQP = r.bf(BL.dQP);
+    float* dQP2 = dQP + (int64_t)B * D;
+    if ((rc = scorer_gemm(r.bf(BL.dGQ), B, D, D, r.bf(BL.WgT), D, D, nullptr, 0, dQP, D, wsplit, st))) return rc;
+    if ((rc = scorer_gemm(r.bf(BL.dBQ), B, D, D, r.bf(BL.WbqT), D, D, nullptr, 0, dQP2, D, wsplit, st))) return rc;
+    hipLaunchKernelGGL(k_add_inplace, blocks_of((int64_t)B * D), dim3(256), 0, st, dQP, dQP2, (int64_t)B * D);
+    hipLaunchKernelGGL(k_act_bwd, blocks_of((int64_t)B * D), dim3(256), 0, st, dQP, n.q_proj, (int64_t)B, D, 1, (const int64_t*)nullptr);
+    EVI_LAUNCH_CHECK();
+    if ((rc = tn_gemm(dQP, D, b->question_emb, D, B, grad(g->query_w), 0, BL, bws, st))) return rc;
+    if ((rc = colsum_into(dQP, B, D, grad(g->query_b), 0, BL, bws, st))) return rc;
+    // the head
+    hipLaunchKernelGGL(k_head_grads, dim3(H), dim3(256), 0, st, w->state4_w, w->state4_b, w->score_w, r.bf(BL.ysum), r.bf(BL.ssum), H,
+                       grad(g->state4_w), grad(g->state4_b), grad(g->score_w), grad(g->score_b));
+    EVI_LAUNCH_CHECK();
+    return EVI_OK;
+}
+
+// The forward (bw null) or the backward of one batch, stage by stage
+static int retriever_run(const EviRetrieverWeights* w, const EviRetrieverBatch* b, int direction_mode,
+                         const EviRetrieverOutput* out, void* workspace, size_t workspace_bytes, void* stream,
+                         const BwdCtx* bw) {
+    Run r{};
+    int rc = validate(r, w, b, direction_mode, out, workspace, workspace_bytes, bw);
+    if (rc != EVI_OK || r.E == 0) return rc;
+    resolve(r, workspace, stream);
+    const SingleProductScope precision_scope(b->matmul_precision);
+    if (!r.nodes_replayed && (rc = node_forward(r))) return rc;
+    if (!r.prep && (rc = derive_weights(w, r.D, r.H, r.F, r.wts, r.st))) return rc;
+    // node_repr Wc^T: a node-level product, made once the Wc block is there
+    if (!r.nodes_replayed &&
+        (rc = scorer_gemm(r.n.node_repr, r.N, r.D, r.D, r.wts.wc, r.H, r.D, nullptr, 0, r.n.hcn, r.H, r.wsplit, r.st, r.planes.wc)))
+        return rc;
+    if (bw && (rc = backward_setup(r))) return rc;
+    if (r.pairs && (rc = pair_rows(r))) return rc;
     // (r03: alternating the chunks between the caller's stream and a side stream, so that one chunk's HBM-bound per-edge kernels
     // run under the other's GEMMs, was built and measured: 3.471 -> 3.427 ms per forward, nothing once the pair rows above were
     // in.  The GEMM workgroup owns its CU — 2 x 250 of the 512 VGPRs of every SIMD, 128 KB of LDS — so nothing co-resides with it
     // and two streams only interleave whole kernels.  Removed.)
-    for (int64_t e0 = 0; e0 < E; e0 += L.ec) {
-        const int64_t ec = (E - e0) < L.ec ? (E - e0) : L.ec;
-        EdgeFeatArgs a;
-        a.edge_index = b->edge_index;
-        a.E = E;
-        a.edge_batch = b->edge_batch;
-        a.edge_attr = b->edge_attr;
-        a.rel_by_edge = L.dedupe ? 0 : 1;
-        a.R = b->num_relations;
-        a.node_repr = node_repr;
-        a.rel_repr = rel_repr;
-        a.gate_q = gate_q;
-        a.bias_q = bias_q;
-        a.node_struct = ns;
-        a.F = F;
-        a.struct_wt = wt;
-        a.struct_b = w->struct_b;
-        a.struct_ln_w = w->struct_ln_w;
-        a.struct_ln_b = w->struct_ln_b;
-        a.struct_gate_w = w->struct_gate_w;
-        a.struct_gate_b = w->struct_gate_b;
-        a.D = D;
-        a.e_begin = e0;
-        a.e_count = ec;
-        a.dir_fwd = dir_fwd;
-        a.dir_bwd = dir_bwd;
-        const int64_t M = (int64_t)dirs * ec;
-        float *pP = F32(L.P), *pRCX = F32(L.RCX), *pXS = F32(L.XS), *pAux = F32(L.aux), *pPA = F32(L.PA), *pRC = F32(L.RC), *pSB = F32(L.SB);
-        if (saved) {
-            float* q = saved + (size_t)e0 * saved_floats_per_edge(D, H, dirs);
-            pP = q, q += ec * D;
-            pRCX = q, q += ec * D;
-            pXS = q, q += M * D;
-            pPA = q, q += ec * H;
-            pRC = q, q += ec * H;
-            pSB = q, q += M * H;
-            pAux = q;
-        }
-        a.P = pP;
-        a.RCX = pairs ? nullptr : pRCX;
-        a.XS = pXS;
-        a.aux = pAux;
-        static const int ef_threads = [] {
-            const char* e = getenv("EVI_EF_THREADS");
-            const int n = e ? atoi(e) : 0;
-            return (n >= 64 && n <= 1024 && n % 64 == 0) ? n : 1024;
-        }();
-        const int ef_waves = ef_threads / 64;
-        int64_t blocks = (ec + ef_waves - 1) / ef_waves;  // one edge per wave
-        if (blocks > 512) blocks = 512;   // 2 blocks per CU fit in LDS
-        if (!replay) {
-        const int tok = timing_begin(kTimeEdge, st);
-        EVI_DPL_DISPATCH(dpl_d, {
-            static thread_local bool attr = false;
-            if (!attr) {
-                EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_edge_features<DPL>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr = true;
-            }
-            hipLaunchKernelGGL(k_edge_features<DPL>, dim3((unsigned)blocks), dim3(ef_threads), feat_lds, st, a);
-        });
-        timing_end(tok, st);
-        EVI_LAUNCH_CHECK();
-        // (r03: writing P / RCX / XS as bf16 hi / lo planes and multiplying them on a pre-split LDS-DMA GEMM was wired in here,
-        // bit-identical, and measured with rocprofv3 on this batch: 288.8 us per launch against 285.0 us for this kernel, the edge
-        // kernel 344 against 330 us — no gain inside the pipeline, so that kernel and its entry points were removed)
-        if ((rc = scorer_gemm(pP, ec, D, D, wa, H, D, nullptr, 0, pPA, H, wsplit, st, planes(PL.p_wa)))) return rc;
-        if (!pairs && (rc = scorer_gemm(pRCX, ec, D, D, wc, H, D, nullptr, 0, pRC, H, wsplit, st, planes(PL.p_wc)))) return rc;
-        if ((rc = scorer_gemm(pXS, M, D, D, wb, H, D, w->state0_b, 0, pSB, H, wsplit, st, planes(PL.p_wb)))) return rc;
-        }
-        CombineArgs c;
-        c.edge_index = b->edge_index;
-        c.E = E;
-        c.e_begin = e0;
-        c.e_count = ec;
-        c.PA = pPA;
-        c.RC = pairs ? reinterpret_cast<float*>(base + L.pair_rc) : pRC;
-        c.pair_table = pairs ? I32(L.pair_table) : nullptr;
-        c.edge_attr = b->edge_attr;
-        c.edge_batch = b->edge_batch;
-        c.R = b->num_relations;
-        c.SB = pSB;
-        c.HcN = hcn;
-        c.aux = pAux;
-        c.wd = wd;
-        c.ln_w = w->state_ln_w;
-        c.ln_b = w->state_ln_b;
-        c.H = H;
-        c.dir_fwd = dir_fwd;
-        c.dir_bwd = dir_bwd;
-        c.h1c = out->edge_features ? F32(L.h1n) : nullptr;
-        c.v = vhead;
-        c.edge_bias = b->edge_bias;
-        c.drop_thr = drop_thr;
-        c.drop_scale = drop_thr ? 65536.0f / (float)(65536u - drop_thr) : 1.0f;
-        c.drop_seed = b->dropout_seed;
-        c.logits = out->logits;
-        c.logits_fwd = out->logits_fwd;
-        c.logits_bwd = out->logits_bwd;
-        const dim3 cgrid((unsigned)((ec + 3) / 4));
-        if (!replay) {
-            if (c.h1c) {
-                EVI_DPL_DISPATCH(dpl_h, hipLaunchKernelGGL((k_state_combine<DPL, true>), cgrid, dim3(256), 0, st, c));
-            } else {
-                EVI_DPL_DISPATCH(dpl_h, hipLaunchKernelGGL((k_state_combine<DPL, false>), cgrid, dim3(256), 0, st, c));
-            }
-        }
-        EVI_LAUNCH_CHECK();
-        if (out->edge_features && !replay)  // state_net.4 on the combined rows, straight into the caller's [E, H] output
-            if ((rc = scorer_gemm(F32(L.h1n), ec, H, H, w->state4_w, H, H, w->state4_b, 0, out->edge_features + e0 * H, H, wsplit,
-                                  st, planes(PL.p_s4))))
-                return rc;
-        if (!bw) continue;
-        // ---- backward of this chunk (scorer_bwd.hpp) ----------------------------------------------------------------
-        const EviRetrieverWeights* g = bw->g;
-        CombineBwdArgs cb;
-        cb.f = c;
-        cb.dlogits = bw->dlogits;
-        cb.DZ = BF(BL.DZ);
-        cb.DPA = BF(BL.DPA);
-        cb.DRC = BF(BL.DRC);
-        cb.DDF = BF(BL.DDF);
-        cb.daux = BF(BL.daux);
-        cb.part = BF(BL.partC);
-        EVI_DPL_DISPATCH(dpl_h, hipLaunchKernelGGL((k_combine_bwd<DPL>), dim3(BL.gridC), dim3(256), 0, st, cb));
-        EVI_LAUNCH_CHECK();
-        {   // column partials: [gridC][5][H] then [gridC] — reduce each of the five vectors and S (accumulating over chunks)
-            float* dst5[5] = {G(g->state_ln_w), G(g->state_ln_b), BF(BL.ysum), BF(BL.gwd), G(g->state0_b)};
-            // the partial rows interleave the five vectors: one [gridC][5H] table, reduced straight into the five gradients
-            if ((rc = colsum_into_multi(BF(BL.partC), BL.gridC, 5, H, dst5, BL, bws, st))) return rc;
-            if ((rc = colsum_into(BF(BL.partC) + (int64_t)BL.gridC * 5 * H, BL.gridC, 1, BF(BL.ssum), 1, BL, bws, st))) return rc;
-        }
-        // d(state_net.0 inputs): dP = dPA Wa, dRCX = dRC Wc, dXS = dz Wb   (NT GEMMs against the transposed blocks)
-        if ((rc = scorer_gemm(BF(BL.DPA), ec, H, H, BF(BL.WaT), D, H, nullptr, 0, BF(BL.dP), D, wsplit, st))) return rc;
-        if ((rc = scorer_gemm(BF(BL.DRC), ec, H, H, BF(BL.WcT), D, H, nullptr, 0, BF(BL.dRCX), D, wsplit, st))) return rc;
-        if ((rc = scorer_gemm(BF(BL.DZ), M, H, H, BF(BL.WbT), D, H, nullptr, 0, BF(BL.dXS), D, wsplit, st))) return rc;
-        // weight blocks of state_net.0: dWa += dPA^T P, dWc += dRC^T RCX, dWb += dz^T XS
-        if ((rc = tn_gemm(BF(BL.DPA), H, pP, D, ec, BF(BL.gWa), 1, BL, bws, st))) return rc;
-        if ((rc = tn_gemm(BF(BL.DRC), H, pRCX, D, ec, BF(BL.gWc), 1, BL, bws, st))) return rc;
-        if ((rc = tn_gemm(BF(BL.DZ), H, pXS, D, M, BF(BL.gWb), 1, BL, bws, st))) return rc;
-        EdgeBwdArgs eb;
-        eb.f = a;
-        eb.dP = BF(BL.dP);
-        eb.dRCX = BF(BL.dRCX);
-        eb.dXS = BF(BL.dXS);
-        eb.daux = BF(BL.daux);
-        eb.DH = BF(BL.DH);
-        eb.DT = BF(BL.DT);
-        // with a relation table the three uses of d r_ctx are formed from ONE stored array (DBQ) by k_segment_rowsum_mul
-        eb.DRR = L.dedupe ? nullptr : BF(BL.DRR);
-        eb.DGQ = L.dedupe ? nullptr : BF(BL.DGQ);
-        eb.DBQ = BF(BL.DBQ);
-        eb.DU = BF(BL.DU);
-        eb.SX = BF(BL.SX);
-        eb.part = BF(BL.partE);
-        {
-            const size_t lds = (size_t)(F + 4) * D * sizeof(float);
-            EVI_DPL_DISPATCH(dpl_d, {
-                static thread_local bool attr = false;
-                if (!attr) {
-                    EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_edge_struct_bwd<DPL>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    attr = true;
-                }
-                hipLaunchKernelGGL(k_edge_struct_bwd<DPL>, dim3(BL.gridE), dim3(BL.wavesE * 64), lds, st, eb);
-                const unsigned gt = (unsigned)((ec + 3) / 4 < 8192 ? (ec + 3) / 4 : 8192);
-                hipLaunchKernelGGL(k_edge_translate_bwd<DPL>, dim3(gt > 0 ? gt : 1), dim3(256), 0, st, eb);
-            });
-            EVI_LAUNCH_CHECK();
-            // the per-wave partial table [gridE * waves][4 D] -> one row (two ordered stages), then into the four gradients
-            const int64_t prow = (int64_t)BL.gridE * BL.wavesE;
-            float* dst4[4] = {G(g->struct_ln_w), G(g->struct_ln_b), G(g->struct_gate_w), G(g->struct_b)};
-            if ((rc = colsum_into_multi(BF(BL.partE), prow, 4, D, dst4, BL, bws, st))) return rc;
-            if ((rc = colsum_into(BF(BL.partE) + prow * 4 * D, prow, 1, G(g->struct_gate_b), 1, BL, bws, st))) return rc;
-        }
-        // struct_proj.0: weight [D, F] += dU^T SX (its bias gradient, the column sums of dU, came with the kernel's partials)
-        if ((rc = tn_gemm(BF(BL.DU), D, BF(BL.SX), F, M, G(g->struct_w), 1, BL, bws, st))) return rc;
+    for (int64_t e0 = 0; e0 < r.E; e0 += r.L.ec) {
+        const Chunk ch = chunk_at(r, e0);
+        if (!r.replay && (rc = chunk_forward(r, ch))) return rc;
+        if (bw && (rc = chunk_backward(r, ch))) return rc;
     }
-    if (!bw) return EVI_OK;
-    // ---- backward: once per batch ----------------------------------------------------------------------------------
-    {
-        const EviRetrieverWeights* g = bw->g;
-        auto blocks_of = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-        // nodes: gather the per-edge gradients through the CSR, add the Wc path (HcN = node_repr Wc^T)
-        hipLaunchKernelGGL(k_node_gather_grad, dim3((unsigned)((N * ((D + 255) / 256 + (H + 255) / 256) + 3) / 4)), dim3(256), 0, st, in_ptr, in_eid, out_ptr,
-                           out_eid, BF(BL.DH), BF(BL.DT), D, BF(BL.DDF), H, BF(BL.dNR), BF(BL.dHcN), (int64_t)N);
-        EVI_LAUNCH_CHECK();
-        if ((rc = scorer_gemm(BF(BL.dHcN), N, H, H, BF(BL.WcT), D, H, nullptr, 0, BF(BL.tmpN), D, wsplit, st))) return rc;
-        // dNR += the Wc path; the id-0 rows set aside for the non-text embedding (into tmpN, in place); tanh backward: one pass
-        hipLaunchKernelGGL(k_node_grad_finish, blocks_of((N * D + 3) / 4), dim3(256), 0, st, BF(BL.dNR), BF(BL.tmpN), node_repr,
-                           b->node_embedding_ids, N, D, BF(BL.tmpN));
-        if ((rc = tn_gemm(BF(BL.dHcN), H, node_repr, D, N, BF(BL.gWc), 1, BL, bws, st))) return rc;
-        hipLaunchKernelGGL(k_merge_state0, dim3(H), dim3(256), 0, st, BF(BL.gWa), BF(BL.gWb), BF(BL.gWc), BF(BL.gwd), H, D,
-                           G(g->state0_w));
-        // the non-text embedding: its projection replaced every node row with embedding id 0
-        float* dnt = BF(BL.dnt);
-        if ((rc = colsum_into(BF(BL.tmpN), N, D, dnt, 0, BL, bws, st))) return rc;
-        hipLaunchKernelGGL(k_act_bwd, blocks_of(D), dim3(256), 0, st, dnt, non_text, (int64_t)1, D, 1, (const int64_t*)nullptr);
-        EVI_LAUNCH_CHECK();
-        if ((rc = scorer_gemm(dnt, 1, D, D, BF(BL.WeT), D, D, nullptr, 0, G(g->non_text_emb), D, wsplit, st))) return rc;
-        // entity_proj: dpre = dNR (1 - NR^2), rows with id 0 dropped — done by k_node_grad_finish above
-        if ((rc = tn_gemm(BF(BL.dNR), D, b->node_embeddings, D, N, G(g->entity_w), 0, BL, bws, st))) return rc;
-        if ((rc = tn_gemm(dnt, D, w->non_text_emb, D, 1, G(g->entity_w), 1, BL, bws, st))) return rc;
-        if ((rc = colsum_into(BF(BL.dNR), N, D, G(g->entity_b), 0, BL, bws, st))) return rc;
-        hipLaunchKernelGGL(k_add_inplace, blocks_of(D), dim3(256), 0, st, G(g->entity_b), dnt, (int64_t)D);
-        // relation_proj
-        if (L.dedupe) {
-            const int64_t R = b->num_relations;
-            // d rel_repr[r] = sum over the edges of relation r of d r_ctx[e] * gate_q[graph(e)]
-            if ((rc = segment_rowsum_mul_into(BF(BL.DBQ), D, bw->rel_ptr, bw->rel_perm, R, E, nullptr, BF(BL.dRRu), gate_q, b->edge_batch,
-                                              (int64_t)B - 1, BL, bws, st)))
-                return rc;
-            hipLaunchKernelGGL(k_act_bwd, blocks_of(R * D), dim3(256), 0, st, BF(BL.dRRu), rel_repr, R, D, 1, (const int64_t*)nullptr);
-            EVI_LAUNCH_CHECK();
-            if ((rc = tn_gemm(BF(BL.dRRu), D, rel_rows, D, R, G(g->relation_w), 0, BL, bws, st))) return rc;
-            if ((rc = colsum_into(BF(BL.dRRu), R, D, G(g->relation_b), 0, BL, bws, st))) return rc;
-        } else {
-            hipLaunchKernelGGL(k_act_bwd, blocks_of(E * D), dim3(256), 0, st, BF(BL.DRR), rel_repr, E, D, 1, (const int64_t*)nullptr);
-            EVI_LAUNCH_CHECK();
-            if ((rc = tn_gemm(BF(BL.DRR), D, b->edge_embeddings, D, E, G(g->relation_w), 0, BL, bws, st))) return rc;
-            if ((rc = colsum_into(BF(BL.DRR), E, D, G(g->relation_b), 0, BL, bws, st))) return rc;
-        }
-        // question side: gate (sigmoid) and bias (tanh) of the projected question, then query_proj (tanh)
-        if (L.dedupe) {  // d bias_q[g] = sum of d r_ctx over the graph, d gate_q[g] = sum of d r_ctx * rel_repr[relation]: one pass
-            if ((rc = segment_rowsum_mul_into(BF(BL.DBQ), D, b->edge_ptr, nullptr, B, E, BF(BL.dBQ), BF(BL.dGQ), rel_repr, b->edge_attr,
-                                              b->num_relations - 1, BL, bws, st)))
-                return rc;
-        } else {
-            if ((rc = segment_rowsum_into(BF(BL.DGQ), D, b->edge_ptr, nullptr, B, E, BF(BL.dGQ), BL, bws, st))) return rc;
-            if ((rc = segment_rowsum_into(BF(BL.DBQ), D, b->edge_ptr, nullptr, B, E, BF(BL.dBQ), BL, bws, st))) return rc;
-        }
-        hipLaunchKernelGGL(k_act_bwd, blocks_of((int64_t)B * D), dim3(256), 0, st, BF(BL.dGQ), gate_q, (int64_t)B, D, 2, (const int64_t*)nullptr);
-        hipLaunchKernelGGL(k_act_bwd, blocks_of((int64_t)B * D), dim3(256), 0, st, BF(BL.dBQ), bias_q, (int64_t)B, D, 1, (const int64_t*)nullptr);
-        EVI_LAUNCH_CHECK();
-        if ((rc = tn_gemm(BF(BL.dGQ), D, q_proj, D, B, G(g->q_gate_w), 0, BL, bws, st))) return rc;
-        if ((rc = tn_gemm(BF(BL.dBQ), D, q_proj, D, B, G(g->q_bias_w), 0, BL, bws, st))) return rc;
-        if ((rc = colsum_into(BF(BL.dGQ), B, D, G(g->q_gate_b), 0, BL, bws, st))) return rc;
-        if ((rc = colsum_into(BF(BL.dBQ), B, D, G(g->q_bias_b), 0, BL, bws, st))) return rc;
-        float* dQP = BF(BL.dQP);
-        float* dQP2 = dQP + (int64_t)B * D;
-        if ((rc = scorer_gemm(BF(BL.dGQ), B, D, D, BF(BL.WgT), D, D, nullptr, 0, dQP, D, wsplit, st))) return rc;
-        if ((rc = scorer_gemm(BF(BL.dBQ), B, D, D, BF(BL.WbqT), D, D, nullptr, 0, dQP2, D, wsplit, st))) return rc;
-        hipLaunchKernelGGL(k_add_inplace, blocks_of((int64_t)B * D), dim3(256), 0, st, dQP, dQP2, (int64_t)B * D);
-        hipLaunchKernelGGL(k_act_bwd, blocks_of((int64_t)B * D), dim3(256), 0, st, dQP, q_proj, (int64_t)B, D, 1, (const int64_t*)nullptr);
-        EVI_LAUNCH_CHECK();
-        if ((rc = tn_gemm(dQP, D, b->question_emb, D, B, G(g->query_w), 0, BL, bws, st))) return rc;
-        if ((rc = colsum_into(dQP, B, D, G(g->query_b), 0, BL, bws, st))) return rc;
-        // the head
-        hipLaunchKernelGGL(k_head_grads, dim3(H), dim3(256), 0, st, w->state4_w, w->state4_b, w->score_w, BF(BL.ysum), BF(BL.ssum), H,
-                           G(g->state4_w), G(g->state4_b), G(g->score_w), G(g->score_b));
-        EVI_LAUNCH_CHECK();
-    }
-    return EVI_OK;
+    return bw ? batch_backward(r) : EVI_OK;
 }
 
 extern "C" int evi_retriever_forward(const EviRetrieverWeights* w, const EviRetrieverBatch* b, int direction_mode,
@@ -1584,12 +1686,17 @@ extern "C" size_t evi_retriever_saved_bytes_full(int64_t N, int64_t E, int B, in
     return align_up(edges, 256) + node_keep_layout(N, E, B, D, H, F, num_relations, dedupe).total;
 }
 
+// the backward's workspace: the forward's, the backward's, the recomputed logits (3 x [E])
+static size_t backward_bytes(const FwdLayout& L, const BwdLayout& BL, int64_t E) {
+    return align_up(L.total, 256) + BL.total + align_up((size_t)(E > 0 ? E : 1) * 3 * 4, 256);
+}
+
 extern "C" size_t evi_retriever_backward_workspace_bytes(int64_t N, int64_t E, int B, int D, int H, int dde_rounds,
                                                          int dde_reverse_rounds, int64_t num_relations) {
     if (N < 0 || E < 0 || B < 1 || D < 1 || H < 1) return 0;
     const int F = 2 * 2 * (1 + dde_rounds + dde_reverse_rounds);
     const FwdLayout L = fwd_layout(N, E, B, D, H, F, num_relations, 2);
-    return align_up(L.total, 256) + bwd_layout(N, E, B, D, H, F, L.dedupe ? num_relations : 0, L.ec).total + align_up((size_t)(E > 0 ? E : 1) * 3 * 4, 256);
+    return backward_bytes(L, bwd_layout(N, E, B, D, H, F, L.dedupe ? num_relations : 0, L.ec), E);
 }
 
 extern "C" int evi_retriever_backward(const EviRetrieverWeights* w, const EviRetrieverBatch* b, int direction_mode,
@@ -1603,19 +1710,20 @@ extern "C" int evi_retriever_backward(const EviRetrieverWeights* w, const EviRet
     EVI_REQUIRE(b->num_graphs >= 1 && D >= 1 && H >= 1, "evi_retriever_backward: bad sizes");
     if (E == 0) return EVI_OK;
     const int F = 2 * 2 * (1 + w->dde_rounds + w->dde_reverse_rounds);
-    const FwdLayout L = fwd_layout(N, E, b->num_graphs, D, H, F, b->num_relations, 2);
-    EVI_REQUIRE(!L.dedupe || (rel_perm && rel_ptr), "evi_retriever_backward: rel_perm / rel_ptr are required when num_relations is given");
-    const size_t need = evi_retriever_backward_workspace_bytes(N, E, b->num_graphs, D, H, w->dde_rounds, w->dde_reverse_rounds, b->num_relations);
+    BwdCtx ctx{dlogits, grads, rel_perm, rel_ptr, nullptr, static_cast<const char*>(saved), saved_bytes};
+    ctx.L = fwd_layout(N, E, b->num_graphs, D, H, F, b->num_relations, 2);
+    EVI_REQUIRE(!ctx.L.dedupe || (rel_perm && rel_ptr), "evi_retriever_backward: rel_perm / rel_ptr are required when num_relations is given");
+    ctx.BL = bwd_layout(N, E, b->num_graphs, D, H, F, ctx.L.dedupe ? b->num_relations : 0, ctx.L.ec);
+    const size_t fwd_bytes = align_up(ctx.L.total, 256);
+    const size_t need = N < 0 || E < 0 ? 0 : backward_bytes(ctx.L, ctx.BL, E);  // (bad sizes: retriever_run reports them)
     EVI_REQUIRE(workspace, "evi_retriever_backward: null workspace");
     if (workspace_bytes < need) return fail(EVI_ERR_NOMEM, "evi_retriever_backward: workspace %zu B < %zu B", workspace_bytes, need);
     char* base = static_cast<char*>(workspace);
-    const size_t fwd_bytes = align_up(L.total, 256);
-    const BwdLayout BL = bwd_layout(N, E, b->num_graphs, D, H, F, L.dedupe ? b->num_relations : 0, L.ec);
-    float* scratch_logits = reinterpret_cast<float*>(base + fwd_bytes + BL.total);  // the recomputed logits (3 x [E])
+    ctx.ws = base + fwd_bytes;
+    float* scratch_logits = reinterpret_cast<float*>(base + fwd_bytes + ctx.BL.total);  // the recomputed logits (3 x [E])
     EviRetrieverOutput o{};
     o.logits = scratch_logits;
     o.logits_fwd = scratch_logits + E;
     o.logits_bwd = scratch_logits + 2 * E;
-    BwdCtx ctx{dlogits, grads, rel_perm, rel_ptr, base + fwd_bytes, static_cast<const char*>(saved), saved_bytes};
     return retriever_run(w, b, direction_mode, &o, base, fwd_bytes, stream, &ctx);
 }

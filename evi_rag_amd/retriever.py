@@ -209,23 +209,11 @@ class Retriever(nn.Module):
 
     # ---- internals -----------------------------------------------------------------------------------
     def _weights_struct(self) -> _lib.EviRetrieverWeights:
-        p = lambda t: t.detach().data_ptr()  # noqa: E731
         w = _lib.EviRetrieverWeights()
         w.emb_dim, w.hidden_dim, w.num_topics = self.emb_dim, self.hidden_dim, self.num_topics
         w.dde_rounds, w.dde_reverse_rounds = self.dde.num_rounds, self.dde.num_reverse_rounds
-        for name, mod in (("entity", self.entity_proj), ("relation", self.relation_proj), ("query", self.query_proj)):
-            setattr(w, f"{name}_w", p(mod.network[0].weight))
-            setattr(w, f"{name}_b", p(mod.network[0].bias))
-        w.non_text_emb = p(self.non_text_entity_emb.weight)
-        w.q_gate_w, w.q_gate_b = p(self.q_gate[0].weight), p(self.q_gate[0].bias)
-        w.q_bias_w, w.q_bias_b = p(self.q_bias[0].weight), p(self.q_bias[0].bias)
-        w.struct_w, w.struct_b = p(self.struct_proj[0].weight), p(self.struct_proj[0].bias)
-        w.struct_ln_w, w.struct_ln_b = p(self.struct_proj[1].weight), p(self.struct_proj[1].bias)
-        w.struct_gate_w, w.struct_gate_b = p(self.struct_gate_net[0].weight), p(self.struct_gate_net[0].bias)
-        w.state0_w, w.state0_b = p(self.state_net[0].weight), p(self.state_net[0].bias)
-        w.state_ln_w, w.state_ln_b = p(self.state_net[1].weight), p(self.state_net[1].bias)
-        w.state4_w, w.state4_b = p(self.state_net[4].weight), p(self.state_net[4].bias)
-        w.score_w, w.score_b = p(self.score_head.weight), p(self.score_head.bias)
+        for name, param in self._param_fields():
+            setattr(w, name, param.detach().data_ptr())
         w.prepared = None
         return w
 
@@ -296,7 +284,6 @@ class Retriever(nn.Module):
         dev, E, N, B = pack["dev"], pack["E"], pack["N"], pack["B"]
         D, H = self.emb_dim, self.hidden_dim
         logits = torch.empty(E, dtype=torch.float32, device=dev)
-        both = self.direction_mode == "bidirectional"
         logits_fwd = torch.empty(E, dtype=torch.float32, device=dev) if self.direction_mode != "backward" else None
         logits_bwd = torch.empty(E, dtype=torch.float32, device=dev) if self.direction_mode != "forward" else None
         features = torch.empty((E, H), dtype=torch.float32, device=dev) if pack["want_features"] else None
@@ -325,8 +312,6 @@ class Retriever(nn.Module):
         _lib.check(lib.evi_retriever_forward(ctypes.byref(w), ctypes.byref(b), _DIRECTION_CODE[self.direction_mode],
                                              ctypes.byref(o), ws.data_ptr(), ws.numel(),
                                              torch.cuda.current_stream(dev).cuda_stream))
-        if not both:
-            pass
         return logits, logits_fwd, logits_bwd, features
 
     def _launch_backward(self, pack, dlogits: torch.Tensor):

@@ -144,12 +144,26 @@ def test_backward_multi_chunk_batch_matches_finite_differences(dev, monkeypatch)
     assert abs(analytic - numeric) <= 2e-3 * max(1.0, abs(numeric)), (analytic, numeric)
 
 
-@pytest.mark.parametrize("direction_mode", ["bidirectional", "forward"])
-def test_replayed_forward_intermediates_give_the_recomputing_backwards_bits(dev, direction_mode):
+@pytest.mark.parametrize("direction_mode,edge_rows_only", [("bidirectional", False), ("forward", False), ("bidirectional", True)],
+                         ids=["bidirectional", "forward", "bidirectional-edge-rows-only"])
+def test_replayed_forward_intermediates_give_the_recomputing_backwards_bits(dev, monkeypatch, direction_mode, edge_rows_only):
     """keep_forward_intermediates (the forward's per-edge rows kept in `saved`, the backward replays them) against the
     backward that recomputes the forward: same kernels on the same values, so every gradient is equal bit for bit — over
-    two chunks and in a single-direction mode (a different `saved` layout)."""
+    two chunks and in a single-direction mode (a different `saved` layout).  edge_rows_only: `saved` sized by
+    evi_retriever_saved_bytes, without room for the node-level results, so the backward replays the per-edge rows and
+    recomputes the node-level forward."""
+    from evi_rag_amd import _lib
     from evi_rag_amd.retriever import Retriever
+
+    sized = []
+    if edge_rows_only:
+        lib = _lib.load()
+
+        def edge_rows_only_bytes(N, E, B, D, H, rounds, rev, R, mode):
+            sized.append(E)
+            return lib.evi_retriever_saved_bytes(E, D, H, mode)
+
+        monkeypatch.setattr(lib, "evi_retriever_saved_bytes_full", edge_rows_only_bytes)
 
     D = H = 64
     sb = synthetic.make_batch(24, nodes_per_graph=900, edges_per_graph=3000, emb_dim=D, num_relations=50, seed=3)
@@ -169,6 +183,7 @@ def test_replayed_forward_intermediates_give_the_recomputing_backwards_bits(dev,
     for n in grads[True]:
         assert torch.equal(grads[True][n], grads[False][n]), n
     assert float(grads[True]["state_net.0.weight"].abs().max()) > 0
+    assert bool(sized) == edge_rows_only
 
 
 def _dropout_multipliers(seed, E, H, p):

@@ -48,3 +48,53 @@ def test_ops_refuse_cpu_tensors():
         ops.cosine_topk(torch.zeros(2, 16), torch.zeros(4, 16), 2)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         ops.normalize_embeddings(torch.ones(2, 16))
+
+
+# Exact workspace / buffer sizes of the scorer and the top-k scans for a table of shapes (pinned from a build whose layouts
+# were not refactored): a layout change that moves or resizes a field shows up here before it reaches a device.
+# (N, E, B, D, H, dde_rounds, dde_reverse_rounds, num_relations) ->
+#   prepare, forward workspace, backward workspace, saved per direction mode, saved_full per direction mode
+_SCORER_SIZES = [
+    ((100, 300, 2, 64, 64, 2, 2, 16),  # E < 1024: no pair rows
+     (210688, 855296, 4317440, (619200, 463200, 463200), (690688, 534784, 534784))),
+    ((5000, 20000, 8, 64, 32, 2, 2, 0),  # R = 0: per-edge relation rows
+     (144896, 41580288, 156733952, (31040000, 23200000, 23200000), (38647808, 30807808, 30807808))),
+    ((500, 2000, 4, 32, 64, 1, 0, 5000),  # R > E: per-edge relation rows
+     (96000, 4195840, 15914496, (3104000, 2320000, 2320000), (3599104, 2815232, 2815232))),
+    ((10000, 50000, 128, 64, 64, 2, 2, 40000),  # B R > 2^22: relation table without pair rows
+     (210688, 143860992, 462261248, (103200000, 77200000, 77200000), (130179840, 104179968, 104179968))),
+    ((20000, 60000, 16, 64, 64, 2, 2, 50),  # pair rows
+     (210688, 153175552, 527213824, (123840000, 92640000, 92640000), (136038912, 104838912, 104838912))),
+    ((120000, 600000, 32, 128, 96, 2, 2, 500),  # E > 262144: three edge chunks
+     (683008, 1190206976, 5217041408, (2160000000, 1617600000, 1617600000), (2283442176, 1741042176, 1741042176))),
+    ((1, 0, 1, 4, 4, 0, 0, 0),  # no edges
+     (6656, 10496, 27648, (144, 104, 104), (4096, 4096, 4096))),
+]
+# (Q, N, D, k) -> GEMM top-k workspace, two-stage workspace
+_TOPK_SIZES = [
+    ((1, 1000, 64, 10), (140544, 345856)),
+    ((32, 1 << 20, 384, 100), (4920064, 268766720)),
+    ((64, 5000, 768, 500), (10040576, 2354688)),
+    ((7, 300000, 1024, 50), (1093120, 77052672)),
+]
+
+
+@pytest.mark.parametrize("shape,want", _SCORER_SIZES)
+def test_scorer_layout_sizes_are_pinned(monkeypatch, shape, want):
+    for var in ("EVI_EDGE_CHUNK", "EVI_SCORER_PAIRS", "EVI_SCORER_GEMM"):
+        monkeypatch.delenv(var, raising=False)
+    lib = _lib.load()
+    N, E, B, D, H, rounds, rev, R = shape
+    got = (lib.evi_retriever_prepare_bytes(D, H, rounds, rev),
+           lib.evi_retriever_forward_workspace_bytes(N, E, B, D, H, rounds, rev, R),
+           lib.evi_retriever_backward_workspace_bytes(N, E, B, D, H, rounds, rev, R),
+           tuple(lib.evi_retriever_saved_bytes(E, D, H, mode) for mode in range(3)),
+           tuple(lib.evi_retriever_saved_bytes_full(N, E, B, D, H, rounds, rev, R, mode) for mode in range(3)))
+    assert got == want
+
+
+@pytest.mark.parametrize("shape,want", _TOPK_SIZES)
+def test_topk_workspace_sizes_are_pinned(shape, want):
+    lib = _lib.load()
+    got = (lib.evi_cosine_topk_gemm_workspace_bytes(*shape), lib.evi_cosine_topk_two_stage_workspace_bytes(*shape))
+    assert got == want
