@@ -22,6 +22,7 @@ EVI_ERR_NOMEM = -12
 EVI_ERR_HIP = -5
 EVI_ERR_UNSUPPORTED = -95
 EVI_TOPK_MAX_K = 2048
+EVI_BFS_CHAIN_MAX_LENGTH = 32
 
 _P = c_void_p
 
@@ -135,6 +136,9 @@ _SIGNATURES = {
     "evi_retriever_forward_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int64]),
     "evi_retriever_forward": (c_int, [POINTER(EviRetrieverWeights), POINTER(EviRetrieverBatch), c_int,
                                       POINTER(EviRetrieverOutput), _P, c_size_t, _P]),
+    "evi_bfs_chains_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    "evi_bfs_chains": (c_int, [c_int] + [_P] * 5 + [c_int64] * 4 + [_P] * 6 + [c_int] * 11 + [_P] * 6
+                       + [_P, c_size_t, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -192,6 +192,18 @@ def evaluate(cfg: Mapping[str, Any], *, device: Optional[str] = None) -> Tuple[D
     with torch.no_grad():
         result = evaluator.run(loader)
     metrics = dict(result["metrics"])
+    # src/eval.py:376-379: candidate chains from the g_agent cache this run has just built (a no-op when the
+    # `bfs_chain_eval` block is absent or disabled).  The reference's materialisation callback writes that cache at the
+    # end of the test epoch; here it is written for the chain export, so a run without the block writes what it did before.
+    from .bfs_chains import maybe_build_bfs_chains
+
+    if bool((cfg.get("bfs_chain_eval") or {}).get("enabled", False)):
+        from .g_agent import GAgentBuilder
+
+        for cb in callbacks:
+            if isinstance(cb, GAgentBuilder):
+                cb.save(cb.cfg.output_path)
+    metrics.update(maybe_build_bfs_chains(cfg))
 
     if metrics:
         filename = "metrics.json"

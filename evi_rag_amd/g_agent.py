@@ -410,4 +410,102 @@ class GAgentBuilder:
         return rec
 
 
-__all__ = ["GAgentSettings", "GAgentSample", "GAgentBuilder", "SCORE_MODE_LOGITS", "SCORE_MODE_NODE_SOFTMAX"]
+# ---- reading a g_agent cache back (src/data/g_agent_dataset.py:96-135,300-334) ------------------------------------------
+_RECORD_KEYS = ("sample_id", "question", "question_emb", "edge_relations", "edge_scores", "edge_labels", "edge_head_locals",
+                "edge_tail_locals", "node_entity_ids", "node_embedding_ids", "start_entity_ids", "start_node_locals",
+                "answer_entity_ids", "answer_node_locals", "pair_start_node_locals", "pair_answer_node_locals",
+                "pair_edge_local_ids", "pair_edge_counts", "pair_shortest_lengths", "gt_path_edge_local_ids", "gt_path_exists",
+                "is_answer_reachable")
+
+
+def _record_to_sample(record: Dict[str, Any]) -> GAgentSample:
+    """The reference's record parser, restricted to the checks that bear on the fields a consumer of the cache reads."""
+    missing = [k for k in _RECORD_KEYS if k not in record]
+    if missing:
+        raise ValueError(f"g_agent record missing keys: {missing}")
+    sid = record.get("sample_id")
+
+    def as_long(key):
+        return torch.as_tensor(record[key], dtype=torch.long).view(-1)
+
+    ent = as_long("node_entity_ids")
+    heads, tails = as_long("edge_head_locals"), as_long("edge_tail_locals")
+    rels = as_long("edge_relations")
+    scores = torch.as_tensor(record["edge_scores"], dtype=torch.float32).view(-1)
+    labels = torch.as_tensor(record["edge_labels"], dtype=torch.float32).view(-1)
+    num_nodes, num_edges = ent.numel(), heads.numel()
+    if torch.unique(ent).numel() != num_nodes:
+        raise ValueError(f"node_entity_ids must be unique per sample: {sid}")
+    for name, t in (("edge_tail_locals", tails), ("edge_relations", rels), ("edge_scores", scores), ("edge_labels", labels)):
+        if t.numel() != num_edges:
+            raise ValueError(f"{name} length {t.numel()} != num_edges {num_edges} for {sid}")
+    if num_nodes == 0:
+        raise ValueError(f"g_agent record has no nodes: {sid}")
+    if num_edges == 0:
+        raise ValueError(f"g_agent record has no edges: {sid}")
+    for name, t in (("edge_head_locals", heads), ("edge_tail_locals", tails)):
+        if bool((t < 0).any()) or bool((t >= num_nodes).any()):
+            raise ValueError(f"{name} out of range for {sid}")
+    starts, answers = as_long("start_node_locals"), as_long("answer_node_locals")
+    for name, t in (("start_node_locals", starts), ("answer_node_locals", answers)):
+        if t.numel() > 0 and (bool((t < 0).any()) or bool((t >= num_nodes).any())):
+            raise ValueError(f"{name} out of range for {sid}")
+    if (starts.numel() > 0 and answers.numel() > 0) != bool(record["is_answer_reachable"]):
+        raise ValueError(f"is_answer_reachable mismatch for {sid}: declared={bool(record['is_answer_reachable'])}, "
+                         f"computed={bool(starts.numel() > 0 and answers.numel() > 0)}")
+    q = torch.as_tensor(record["question_emb"], dtype=torch.float32)
+    sample = GAgentSample(
+        sample_id=str(record["sample_id"]), question=str(record["question"]), question_emb=q.view(1, -1) if q.dim() == 1 else q,
+        node_entity_ids=ent, node_embedding_ids=as_long("node_embedding_ids"), edge_head_locals=heads, edge_tail_locals=tails,
+        edge_relations=rels, edge_scores=scores, edge_labels=labels, start_entity_ids=as_long("start_entity_ids"),
+        answer_entity_ids=as_long("answer_entity_ids"), gt_path_edge_local_ids=as_long("gt_path_edge_local_ids"),
+        start_node_locals=starts, answer_node_locals=answers, pair_start_node_locals=as_long("pair_start_node_locals"),
+        pair_answer_node_locals=as_long("pair_answer_node_locals"), pair_edge_local_ids=as_long("pair_edge_local_ids"),
+        pair_edge_counts=as_long("pair_edge_counts"), pair_shortest_lengths=as_long("pair_shortest_lengths"),
+        gt_path_exists=bool(record["gt_path_exists"]), is_answer_reachable=bool(record["is_answer_reachable"]),
+        is_dummy_agent=bool(record.get("is_dummy_agent", False)))
+    if sample.start_entity_ids.numel() == 0:
+        raise ValueError(f"g_agent record missing non-empty start_entity_ids: {sid}")
+    return sample
+
+
+def load_g_agent_samples(path, *, drop_unreachable: bool = False) -> List[GAgentSample]:
+    """reference: load_g_agent_samples, src/data/g_agent_dataset.py:300-334.  The cache is read with
+    `torch.load(weights_only=True)`: GAgentBuilder.save writes plain dicts of tensors, so nothing needs unpickling, and a
+    cache that holds pickled objects is refused rather than executed."""
+    path = Path(path).expanduser().resolve()
+    if not path.exists():
+        raise FileNotFoundError(f"g_agent cache not found: {path}")
+    try:
+        payload = torch.load(str(path), map_location="cpu", weights_only=True)
+    except Exception as exc:  # noqa: BLE001 - torch raises several types for unsafe pickles
+        raise ValueError(f"{path} cannot be loaded with weights_only=True ({exc}); a g_agent cache holds plain dicts of "
+                         "tensors, and a file that needs unpickling is refused") from exc
+    if isinstance(payload, dict):
+        raw = payload.get("samples") or []
+    elif isinstance(payload, list):
+        raw = payload
+    else:
+        raise TypeError(f"Unsupported g_agent cache format at {path}: {type(payload)}")
+    if not raw:
+        raise ValueError(f"No samples found in {path}")
+    samples: List[GAgentSample] = []
+    dropped = 0
+    for record in raw:
+        if not isinstance(record, dict):
+            raise TypeError(f"Unsupported g_agent record at {path}: {type(record)}")
+        sample = _record_to_sample(record)
+        if drop_unreachable and not sample.is_answer_reachable:
+            dropped += 1
+            continue
+        samples.append(sample)
+    if drop_unreachable and dropped > 0:
+        log.info("Filtered %d unreachable samples (is_answer_reachable=False) from %s", dropped, path)
+    if not samples:
+        raise ValueError(f"No usable samples loaded from {path} (drop_unreachable={drop_unreachable})")
+    log.info("Loaded g_agent cache %s: %d samples.", path, len(samples))
+    return samples
+
+
+__all__ = ["GAgentSettings", "GAgentSample", "GAgentBuilder", "load_g_agent_samples", "SCORE_MODE_LOGITS",
+           "SCORE_MODE_NODE_SOFTMAX"]

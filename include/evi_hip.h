@@ -692,6 +692,35 @@ int evi_grad_norm(const float* g, int64_t n, float scale, float* norm_out, void*
 int evi_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int64_t step, float grad_scale, const float* grad_norm, float max_norm, void* stream);
 
+/* ---- BFS candidate chains over g_agent samples (csrc/chains.hip) ---------------------------------------------------------
+ * Replaces build_bfs_candidate_chains, src/data/components/bfs_chain_builder.py:49-311, for a flat batch of S samples that
+ * share one set of settings.  Per sample s: nodes [node_ptr[s], node_ptr[s+1]) (node_entity i64), edges
+ * [edge_ptr[s], edge_ptr[s+1]) (sample-local edge_head / edge_tail i32, edge_score f32 (finite), edge_relation i64), seeds
+ * [seed_ptr[s], seed_ptr[s+1]) (sample-local node ids in file order; ids outside [0, nodes) are skipped).  The caller gives
+ * every sample room for rec_ptr[s+1] - rec_ptr[s] chain records (at least its seed count) and for sort_ptr[s+1] -
+ * sort_ptr[s] sort slots (a power of two at least as large as its record room); total_* are the last entries of the four
+ * offset arrays.  With max_total_chains > 0 and min_chain_length <= 1, max(max_total_chains, seeds) records always fit.
+ *
+ * Outputs, sample-major: out_count[s] candidates (<= max_out) in rank order; for candidate r of sample s at o = s*max_out+r:
+ * out_len[o] steps, out_freq[o], out_score[o] (f64 sum in path order), out_steps[o*max_chain_length + k] = (edge << 1) |
+ * direction of step k (direction 1 = the edge walked tail -> head).  out_stats[4s..4s+3] = records the sample needed past
+ * its room (0 when it fitted; then its outputs are empty and the caller sizes it again), levels reached, chains of length
+ * >= min_chain_length enumerated, distinct signatures.
+ * max_branch_per_node < 0 keeps every entry.  lds_records / lds_sort_slots: samples whose record room / sort slots are at
+ * most this keep them in LDS (0 = global memory only; the results do not depend on either).  hash_bits (1..64) narrows the
+ * signature hash, a test knob: equal hashes are always confirmed by comparing full signatures. */
+#define EVI_BFS_CHAIN_MAX_LENGTH 32
+size_t evi_bfs_chains_workspace_bytes(int64_t total_nodes, int64_t total_edges, int64_t total_records, int64_t total_sort_slots);
+int evi_bfs_chains(int num_samples, const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* seed_ptr,
+                   const int64_t* rec_ptr, const int64_t* sort_ptr, int64_t total_nodes, int64_t total_edges,
+                   int64_t total_records, int64_t total_sort_slots, const int32_t* edge_head, const int32_t* edge_tail,
+                   const float* edge_score, const int64_t* edge_relation, const int64_t* node_entity, const int32_t* seeds,
+                   int max_chain_length, int min_chain_length, int max_total_chains, int allow_backward,
+                   int max_branch_per_node, int forbid_edge_revisit, int forbid_node_revisit, int max_out, int lds_records,
+                   int lds_sort_slots, int hash_bits, int32_t* out_count, int32_t* out_len, int32_t* out_freq,
+                   double* out_score, int32_t* out_steps, int64_t* out_stats, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
