@@ -139,6 +139,10 @@ _SIGNATURES = {
     "evi_bfs_chains_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
     "evi_bfs_chains": (c_int, [c_int] + [_P] * 5 + [c_int64] * 4 + [_P] * 6 + [c_int] * 11 + [_P] * 6
                        + [_P, c_size_t, _P]),
+    "evi_mx_quantize_rows": (c_int, [_P, c_int, c_int64, c_int, c_int64, _P, _P, _P]),
+    "evi_mx_pack_weight_bytes": (c_size_t, [c_int, c_int]),
+    "evi_mx_pack_weight": (c_int, [_P, c_int, c_int, c_int, c_int64, _P, _P]),
+    "evi_mx_linear": (c_int, [_P, c_int, c_int64, c_int, c_int64, _P, c_int, _P, _P, c_int, c_int64, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

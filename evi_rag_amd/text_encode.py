@@ -65,7 +65,7 @@ class TextEncoder:
     """Same constructor and `encode` contract as the reference wrapper
     (scripts/text_encode_utils.py:13-67): returns a CPU float32 [n, D] tensor."""
 
-    def __init__(self, model_name: str, device: str, fp16: bool, progress: bool) -> None:
+    def __init__(self, model_name: str, device: str, fp16: bool, progress: bool, *, precision: Optional[str] = None) -> None:
         try:
             from transformers import AutoModel, AutoTokenizer
         except ImportError as exc:
@@ -77,15 +77,41 @@ class TextEncoder:
         self.device = device
         self.dtype = torch.float16 if fp16 else torch.float32
         self.progress = progress
+        self.set_precision(precision)
 
     @classmethod
-    def from_components(cls, tokenizer, model, device: str, fp16: bool = False, progress: bool = False) -> "TextEncoder":
+    def from_components(cls, tokenizer, model, device: str, fp16: bool = False, progress: bool = False, *,
+                        precision: Optional[str] = None) -> "TextEncoder":
         """Build from an already-loaded tokenizer/model (offline use, tests)."""
         self = object.__new__(cls)
         self.tokenizer, self.model, self.device = tokenizer, model, device
         self.dtype = torch.float16 if fp16 else torch.float32
         self.progress = progress
+        self.set_precision(precision)
         return self
+
+    # Precision of the model's linear layers (BASELINE config 5, "fp8 encode"; not in the reference).  None: the model's own
+    # nn.Linear modules.  "mxfp8": every nn.Linear whose in_features is a multiple of 32 is replaced in place by an
+    # evi_rag_amd.mx.MXLinear (weights quantised once to MXFP8, activations quantised inside the block-scaled MFMA GEMM).
+    # Combined with `autocast = torch.bfloat16` that is the config-5 form: attention, LayerNorm and GELU in bf16, the
+    # linears MXFP8 with bf16 results.
+    precision: Optional[str] = None
+
+    def set_precision(self, precision: Optional[str]) -> None:
+        """Switch the linears to MXFP8 ("mxfp8") or back to the original nn.Linear objects (None); clears the graph cache."""
+        if precision not in (None, "mxfp8"):
+            raise ValueError(f"precision must be None or 'mxfp8', got {precision!r}")
+        if precision == self.__dict__.get("precision"):
+            return
+        from . import mx
+
+        swapped = self.__dict__.pop("_mx_swapped", None)
+        if swapped is not None:
+            mx.restore_linears(swapped)
+        if precision == "mxfp8":
+            self._mx_swapped = mx.swap_linears(self.model)
+        self.precision = precision
+        self.__dict__.pop("_graphs", None)
 
     # Reduced-precision forward (BASELINE config 5; not in the reference, whose `fp16` flag only changes the pooling
     # dtype, scripts/text_encode_utils.py:28-30): set to torch.bfloat16 / torch.float16 and the transformer runs under
@@ -184,7 +210,8 @@ class TextEncoder:
         return seen[key] >= max(int(self.graph_after), 1)
 
     def _shape_key(self, host_inputs):
-        return (tuple(sorted((k, tuple(v.shape), str(v.dtype)) for k, v in host_inputs.items())), str(self.autocast), str(self.dtype))
+        return (tuple(sorted((k, tuple(v.shape), str(v.dtype)) for k, v in host_inputs.items())), str(self.autocast), str(self.dtype),
+                str(self.precision))
 
     @torch.no_grad()
     def encode(self, texts: Sequence[str], batch_size: int, show_progress: Optional[bool] = None,

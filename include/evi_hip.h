@@ -721,6 +721,23 @@ int evi_bfs_chains(int num_samples, const int64_t* node_ptr, const int64_t* edge
                    double* out_score, int32_t* out_steps, int64_t* out_stats, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* MXFP8 linear layer on gfx950's block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4), the opt-in fp8 encoder linears.
+ * Format: blocks of 32 consecutive K elements per row; scale exponent e = max(-127, ceil(log2(amax / 448))) (e = -127 for
+ * an all-zero block), scale byte e + 127 (e8m0), elements e4m3fn(x * 2^-e) (OCP, round to nearest even, subnormals kept).
+ * K must be a multiple of 32.  dtype codes: 0 f32, 1 f16, 2 bf16.  A block holding NaN or +-inf has scale 0xFF and every
+ * output that reads it is NaN.
+ * evi_mx_quantize_rows: x [M, K] (row stride ldx) -> out_e4m3 [M, K] u8 and out_scale [M, K / 32] u8, row-major.
+ * evi_mx_pack_weight: an nn.Linear weight [N, K] (row stride ldw) quantised along K into `packed`, an opaque image of
+ *   evi_mx_pack_weight_bytes(N, K) bytes (0 for an invalid shape) in the order the GEMM loads it.
+ * evi_mx_linear: y [M, N] (row stride ldy) = x [M, K] (row stride ldx) * W^T (+ bias f32 [N]), f32 accumulation; the
+ *   activation is quantised inside the kernel as it is staged (no workspace).  Deterministic; M = 0 launches nothing. */
+int evi_mx_quantize_rows(const void* x, int dtype_code, int64_t M, int K, int64_t ldx, uint8_t* out_e4m3, uint8_t* out_scale,
+                         void* stream);
+size_t evi_mx_pack_weight_bytes(int N, int K);
+int evi_mx_pack_weight(const void* w, int dtype_code, int N, int K, int64_t ldw, uint8_t* packed, void* stream);
+int evi_mx_linear(const void* x, int x_dtype_code, int64_t M, int K, int64_t ldx, const uint8_t* packed, int N,
+                  const float* bias_or_null, void* y, int y_dtype_code, int64_t ldy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
