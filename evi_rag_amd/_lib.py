@@ -23,6 +23,7 @@ EVI_ERR_HIP = -5
 EVI_ERR_UNSUPPORTED = -95
 EVI_TOPK_MAX_K = 2048
 EVI_BFS_CHAIN_MAX_LENGTH = 32
+EVI_ORACLE_MAX_KS = 64
 
 _P = c_void_p
 
@@ -139,7 +140,9 @@ _SIGNATURES = {
     "evi_bfs_chains_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
     "evi_bfs_chains": (c_int, [c_int] + [_P] * 5 + [c_int64] * 4 + [_P] * 6 + [c_int] * 11 + [_P] * 6
                        + [_P, c_size_t, _P]),
-    "evi_mx_quantize_rows": (c_int, [_P, c_int, c_int64, c_int, c_int64, _P, _P, _P]),
+    "evi_oracle_answer_hits_workspace_bytes": (c_size_t, [c_int64]),
+    "evi_oracle_answer_hits": (c_int, [c_int] + [_P] * 5 + [c_int64, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "evi_mx_quantize_rows":(c_int, [_P, c_int, c_int64, c_int, c_int64, _P, _P, _P]),
     "evi_mx_pack_weight_bytes": (c_size_t, [c_int, c_int]),
     "evi_mx_pack_weight": (c_int, [_P, c_int, c_int, c_int, c_int64, _P, _P]),
     "evi_mx_linear": (c_int, [_P, c_int, c_int64, c_int, c_int64, _P, c_int, _P, _P, c_int, c_int64, _P]),

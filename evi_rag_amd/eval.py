@@ -6,7 +6,9 @@ without Hydra / Lightning: the SAME `configs/` directory is composed with the sa
 the mirrors in this package), the checkpoint is loaded strictly (src/eval.py:80-111), every (dataset variant, split)
 the run asks for is evaluated with `RetrieverEvaluator` (the test loop of RetrieverModule) over the packed split
 resident in HBM, and `metrics[_<variant>][_<split>].json` lands in `${paths.output_dir}` under the reference's naming
-rules (src/eval.py:381-393).
+rules (src/eval.py:381-393).  A run whose `model._target_` is the reasoner module (`experiment=reasoner_oracle`) takes
+the retriever-oracle path of `reasoner_oracle.py` instead: no checkpoint, no packed split, the persisted
+`eval_retriever/<split>.pt` cache in, the module's `predict_metrics` out.
 
 The config directory is the reference checkout's own `configs/`: `--config-dir DIR` (or `-cd DIR`, Hydra's flag), else
 $EVI_RAG_CONFIG_DIR.  Where the reference reads `<dataset.paths.embeddings>/<split>.lmdb`, this backend reads the
@@ -147,6 +149,29 @@ def _build_callbacks(cfg: Mapping[str, Any], dataset) -> List[Any]:
     return out
 
 
+def is_reasoner_run(cfg: Mapping[str, Any]) -> bool:
+    """Whether `model._target_` names the reasoner module (reference path or this package's) rather than a retriever."""
+    target = str((cfg.get("model") or {}).get("_target_") or "")
+    return hl.REFERENCE_TARGETS.get(target, target) == "evi_rag_amd.reasoner_oracle.ReasonerModule"
+
+
+def _save_metrics(cfg: Mapping[str, Any], run: Mapping[str, Any], split: str, metrics: Dict[str, float]) -> None:
+    """metrics[_<variant>][_<split>].json in ${paths.output_dir} (src/eval.py:381-393)."""
+    if not metrics:
+        log.warning("No metrics were produced; skipping metrics.json.")
+        return
+    filename = "metrics.json"
+    variant = run.get("dataset_variant")
+    if variant:
+        filename = f"metrics_{variant}.json"
+    if bool(run.get("run_all_splits", False)) and split not in (None, ""):
+        filename = (f"metrics_{variant}_" if variant else "metrics_") + f"{split}.json"
+    out_dir = Path(str(cfg["paths"]["output_dir"]))
+    out_dir.mkdir(parents=True, exist_ok=True)
+    (out_dir / filename).write_text(json.dumps(metrics, indent=2))
+    log.info("Metrics saved to %s", out_dir / filename)
+
+
 def evaluate(cfg: Mapping[str, Any], *, device: Optional[str] = None) -> Tuple[Dict[str, float], Dict[str, Any]]:
     """One split of one dataset: the reference's `evaluate` (src/eval.py:311-395)."""
     import torch
@@ -168,6 +193,19 @@ def evaluate(cfg: Mapping[str, Any], *, device: Optional[str] = None) -> Tuple[D
     dev = torch.device(device or "cuda:0")
     if dev.type == "cuda":
         torch.cuda.set_device(dev)  # the evi_* kernels launch on the current device's stream
+
+    if is_reasoner_run(cfg):
+        # a ReasonerModule run (experiment=reasoner_oracle): no checkpoint, no packed split; the module's predict_metrics
+        # are what the reference saves, its callback_metrics being empty for this predict run (src/eval.py:368-375)
+        from .bfs_chains import maybe_build_bfs_chains
+        from .reasoner_oracle import run_oracle_eval
+
+        if dev.type != "cuda":
+            raise RuntimeError("the retriever oracle runs on the GPU (evi_oracle_answer_hits); no CPU fallback")
+        metrics = run_oracle_eval(cfg)
+        metrics.update(maybe_build_bfs_chains(cfg))
+        _save_metrics(cfg, run, split, metrics)
+        return metrics, {"cfg": cfg}
 
     data_cfg = cfg.get("data") or {}
     ds_cfg = cfg["dataset"]
@@ -204,20 +242,7 @@ def evaluate(cfg: Mapping[str, Any], *, device: Optional[str] = None) -> Tuple[D
             if isinstance(cb, GAgentBuilder):
                 cb.save(cb.cfg.output_path)
     metrics.update(maybe_build_bfs_chains(cfg))
-
-    if metrics:
-        filename = "metrics.json"
-        variant = run.get("dataset_variant")
-        if variant:
-            filename = f"metrics_{variant}.json"
-        if bool(run.get("run_all_splits", False)) and split not in (None, ""):
-            filename = (f"metrics_{variant}_" if variant else "metrics_") + f"{split}.json"
-        out_dir = Path(str(cfg["paths"]["output_dir"]))
-        out_dir.mkdir(parents=True, exist_ok=True)
-        (out_dir / filename).write_text(json.dumps(metrics, indent=2))
-        log.info("Metrics saved to %s", out_dir / filename)
-    else:
-        log.warning("No metrics were produced; skipping metrics.json.")
+    _save_metrics(cfg, run, split, metrics)
     return metrics, {"cfg": cfg, "model": model, "dataset": dataset, "callbacks": callbacks,
                      "num_graphs": result["num_graphs"], "queries_per_sec": result["queries_per_sec"]}
 

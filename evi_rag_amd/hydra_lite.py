@@ -44,6 +44,8 @@ REFERENCE_TARGETS: Dict[str, str] = {
     "src.metrics.retriever_metrics.ScoreMargin": "evi_rag_amd.metrics.ScoreMargin",
     "src.metrics.reachability.AnswerReachability": "evi_rag_amd.metrics.AnswerReachability",
     "src.data.components.embedding_store.GlobalEmbeddingStore": "evi_rag_amd.embedding_store.GlobalEmbeddingStore",
+    "src.data.reasoner_oracle_datamodule.ReasonerOracleDataModule": "evi_rag_amd.reasoner_oracle.ReasonerOracleDataModule",
+    "src.models.reasoner_module.ReasonerModule": "evi_rag_amd.reasoner_oracle.ReasonerModule",
 }
 
 _GLOBAL_PACKAGE = re.compile(r"^#\s*@package\s+_global_\s*$")

@@ -721,6 +721,22 @@ int evi_bfs_chains(int num_samples, const int64_t* node_ptr, const int64_t* edge
                    double* out_score, int32_t* out_steps, int64_t* out_stats, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* ---- retriever-oracle answer hits over ranked triplet windows (csrc/oracle.hip) ------------------------------------------
+ * Replaces _oracle_metrics_for_sample, src/models/reasoner_module.py:17-68, for a flat batch of S samples.  Per sample s:
+ * ranked edges [edge_ptr[s], edge_ptr[s+1]) (head_ids / tail_ids i64, rank order), raw answer ids [answer_ptr[s],
+ * answer_ptr[s+1]) (i64, duplicates allowed); total_answers = answer_ptr[S].  ks_host: the nk (1..EVI_ORACLE_MAX_KS)
+ * strictly ascending positive k values, read on the host; max_scan_k: ranks past it are never read.
+ * Outputs: uniq[s] = distinct answer ids; found[s*nk + q] = distinct answer ids that appear as a head or a tail among
+ * ranks 1..min(E_s, max_scan_k, ks_host[q]) (the hit flag is found > 0).  No bound on the answer count: a sample whose
+ * answers (rounded up to a power of two) exceed lds_answers (0..4096; the results do not depend on it) sorts them in its
+ * workspace region.  The workspace is evi_oracle_answer_hits_workspace_bytes(total_answers) bytes (0: none needed). */
+#define EVI_ORACLE_MAX_KS 64
+size_t evi_oracle_answer_hits_workspace_bytes(int64_t total_answers);
+int evi_oracle_answer_hits(int num_samples, const int64_t* edge_ptr, const int64_t* head_ids, const int64_t* tail_ids,
+                           const int64_t* answer_ptr, const int64_t* answer_ids, int64_t total_answers, const int64_t* ks_host,
+                           int nk, int max_scan_k, int lds_answers, int32_t* uniq, int32_t* found, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* MXFP8 linear layer on gfx950's block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4), the opt-in fp8 encoder linears.
  * Format: blocks of 32 consecutive K elements per row; scale exponent e = max(-127, ceil(log2(amax / 448))) (e = -127 for
  * an all-zero block), scale byte e + 127 (e8m0), elements e4m3fn(x * 2^-e) (OCP, round to nearest even, subnormals kept).
