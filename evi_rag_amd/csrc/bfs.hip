@@ -18,8 +18,6 @@
 // (N_g * 4 B per level).  Integer work, L2-latency-bound.
 #include "common.hpp"
 
-#include <stdlib.h>
-
 namespace evi {
 
 constexpr int kBfsThreads = 1024;
@@ -581,10 +579,8 @@ extern "C" int evi_bfs_levels(const int32_t* job_graph, const int64_t* src_ptr, 
     // graph (3 000 nodes, 10 000 edges, both halves: 32 002 ints) for the whole search, one workgroup per CU.  THROUGHPUT (more
     // jobs than CUs): 48 KiB, three workgroups per CU hide each other's row gathers, rows read from the L2 — caching them would
     // cost two thirds of the resident searches (measured at 512 jobs: 70 us uncached x 3 per CU against 87 us cached x 1).
-    // EVI_BFS_CACHE=0 / 1 forces either.
     constexpr int kLdsBig = 34816, kLdsSmall = 12288;
-    bool big = num_jobs <= 256;
-    if (const char* e = getenv("EVI_BFS_CACHE")) big = e[0] == '1';
+    const bool big = num_jobs <= 256;
     const int lds_nodes = big ? kLdsBig : kLdsSmall;
     static thread_local bool attr = false;
     if (!attr) {
@@ -608,9 +604,6 @@ extern "C" int evi_bfs_levels_edges(const int32_t* job_graph, const int64_t* src
     if (num_jobs == 0) return EVI_OK;
     EVI_REQUIRE(job_graph && src_ptr && dist_off && node_ptr && edge_ptr && in_ptr && out_ptr && dist_out, "evi_bfs_levels_edges: null pointer");
     EVI_REQUIRE(E == 0 || edge_index, "evi_bfs_levels_edges: null edge_index");
-    if (const char* e = getenv("EVI_BFS_EDGES"))  // A/B runs: 0 = the CSR-based search for every graph
-        if (e[0] == '0')
-            return evi_bfs_levels(job_graph, src_ptr, src_idx, dist_off, num_jobs, node_ptr, in_ptr, in_nbr, out_ptr, out_nbr, mode, dist_out, stream);
     constexpr int kLds = 12288;  // 48 KiB of dynamic LDS for the graphs that take the CSR-based path; the edge-parallel search
                                  // needs 2 bytes per node of it (its edges live in registers)
     hipLaunchKernelGGL(k_bfs_levels_edges, dim3(num_jobs), dim3(kBfsThreads), kLds * sizeof(int32_t), reinterpret_cast<hipStream_t>(stream),

@@ -208,16 +208,18 @@ __device__ inline uint32_t fp8x2_to_f16x2_scaled(uint32_t w, uint32_t sel) {
 
 // One pass over rows [seg_begin, seg_end) of the shard.
 //   NQB: query blocks of 16 (1 or 2).  U: float4 loads in flight per lane per prefetch group
-//   (U divides D/16).  THREADS: workgroup size (one workgroup per CU: LDS holds the queries).
-//   NT: stream the index with non-temporal loads.
+//   (U divides D/16).  kScanThreads per workgroup (one workgroup per CU: LDS holds the queries).
 // Appends are staged per workgroup in LDS (capq entries per query) and flushed once at the end
 // with one global atomic per query, so the per-query cursors see ~256 atomics per launch instead
 // of one per candidate; entries that do not fit go straight to the global list.
 //   F16: the index is stored as f16 (half the HBM bytes); queries are split hi + lo in f16 and
 //   multiplied on v_mfma_f32_16x16x32_f16 with f32 accumulation.
 //   (F16 == 2: the index is OCP e4m3 with a per-row scale; bytes are widened to f16 in registers.)
-template <int NQB, int U, int THREADS, int NT, int F16>
-__global__ __launch_bounds__(THREADS) void k_cosine_score(
+constexpr int kScanThreads = 1024;
+constexpr int kScanMaxU = 4;  // most loads in flight per lane per group
+
+template <int NQB, int U, int F16>
+__global__ __launch_bounds__(kScanThreads) void k_cosine_score(
     const float* __restrict__ qfrag, const void* __restrict__ idx, int64_t seg_begin,
     int64_t seg_end, int D, int Q, const float* __restrict__ row_scale,
     const float* __restrict__ tau, float* __restrict__ cand_score, int32_t* __restrict__ cand_id,
@@ -225,7 +227,7 @@ __global__ __launch_bounds__(THREADS) void k_cosine_score(
     if (gate_closed(gate)) return;
     extern __shared__ float4 lds_q[];  // [(D/16)*4][NQB*16] float4, then the append staging area
     constexpr int NQ = NQB * 16;
-    constexpr int WAVES = THREADS / 64;
+    constexpr int WAVES = kScanThreads / 64;
     const int tid = threadIdx.x;
     const int chunks = F16 >= 2 ? D / 64 : (F16 ? D / 32 : D / 16);  // 64-byte pieces of a row
     const int qslots = F16 == 3 ? (D / 8) * NQ  // native fp8: two 1-byte pieces per element, D * NQ * 2 bytes
@@ -235,7 +237,7 @@ __global__ __launch_bounds__(THREADS) void k_cosine_score(
     int* lds_id = reinterpret_cast<int*>(lds_sc + kQueryBlock * capq);  // [32][capq]
     {
         const float4* src = reinterpret_cast<const float4*>(qfrag);
-        for (int s = tid; s < qslots; s += THREADS) lds_q[s] = src[s];
+        for (int s = tid; s < qslots; s += kScanThreads) lds_q[s] = src[s];
         if (tid < kQueryBlock) lds_cnt[tid] = 0;
     }
     __syncthreads();
@@ -268,11 +270,6 @@ __global__ __launch_bounds__(THREADS) void k_cosine_score(
     const int groups = chunks / U;
     const float4* lq = lds_q + g * NQ + n;  // + (j*4)*NQ + b*16
 
-    auto ldx = [](const f32x4* p) -> f32x4 {
-        if (NT) return __builtin_nontemporal_load(p);
-        return *p;
-    };
-
     // The wave's work is ONE stream of load groups (U float4 per lane each) that runs across tile
     // boundaries: while group i is multiplied, group i+1 — possibly the first group of the wave's
     // next tile — is already in flight, in a second register set (ping-pong, no copies).  Every
@@ -287,7 +284,7 @@ __global__ __launch_bounds__(THREADS) void k_cosine_score(
     };
     auto load_group = [&](f32x4 (&x)[U], const f32x4* xp, int gi) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) x[u] = ldx(xp + (gi * U + u) * 4);
+        for (int u = 0; u < U; ++u) x[u] = xp[(gi * U + u) * 4];
     };
     f32x4 acc[NQB], acc_lo[NQB];
     auto mul_group = [&](const f32x4 (&x)[U], int gi) {
@@ -503,25 +500,6 @@ static int64_t clamp_seg(int64_t N, int64_t want) {
     return s < 1 ? 1 : s;
 }
 
-struct ScanVariant {
-    int threads, nt, u_cap;
-};
-
-static int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
-
-// Tunables (defaults are the measured best on MI355X; the env overrides exist for
-// tools/scan_variants.py, which A/Bs them in one process).
-static ScanVariant scan_variant() {
-    ScanVariant v;
-    v.threads = env_int("EVI_SCAN_THREADS", 1024);
-    v.nt = env_int("EVI_SCAN_NT", 0);
-    v.u_cap = env_int("EVI_SCAN_U", 4);
-    return v;
-}
-
 struct ScoreArgs {
     int grid;
     size_t lds;
@@ -541,51 +519,33 @@ struct ScoreArgs {
     hipEvent_t ev_start, ev_stop;  // non-null: stamped with the dispatch's begin / end (bench roofline leg)
 };
 
-template <int NQB, int U, int THREADS, int NT, int F16 = 0>
+template <int NQB, int U, int F16>
 static int launch_score(const ScoreArgs& a) {
     static thread_local bool attr_set = false;
     if (!attr_set) {
-        EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cosine_score<NQB, U, THREADS, NT, F16>),
+        EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cosine_score<NQB, U, F16>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
     if (a.ev_start)
-        hipExtLaunchKernelGGL((k_cosine_score<NQB, U, THREADS, NT, F16>), dim3(a.grid), dim3(THREADS), (uint32_t)a.lds, a.st,
+        hipExtLaunchKernelGGL((k_cosine_score<NQB, U, F16>), dim3(a.grid), dim3(kScanThreads), (uint32_t)a.lds, a.st,
                               a.ev_start, a.ev_stop, 0, a.qfrag, a.idx, a.b, a.e, a.D, a.Q, a.row_scale, a.tau, a.cs, a.ci,
                               a.cc, a.cap, a.dense, a.capq, a.gate);
     else
-        hipLaunchKernelGGL((k_cosine_score<NQB, U, THREADS, NT, F16>), dim3(a.grid), dim3(THREADS), a.lds, a.st,
+        hipLaunchKernelGGL((k_cosine_score<NQB, U, F16>), dim3(a.grid), dim3(kScanThreads), a.lds, a.st,
                            a.qfrag, a.idx, a.b, a.e, a.D, a.Q, a.row_scale, a.tau, a.cs, a.ci, a.cc, a.cap,
                            a.dense, a.capq, a.gate);
     EVI_LAUNCH_CHECK();
     return EVI_OK;
 }
 
-template <int NQB, int THREADS, int NT>
+template <int NQB, int F16>
 static int launch_score_u(int U, const ScoreArgs& a) {
     switch (U) {
-        case 8: return launch_score<NQB, 8, THREADS, NT>(a);
-        case 4: return launch_score<NQB, 4, THREADS, NT>(a);
-        case 2: return launch_score<NQB, 2, THREADS, NT>(a);
-        default: return launch_score<NQB, 1, THREADS, NT>(a);
+        case 4: return launch_score<NQB, 4, F16>(a);
+        case 2: return launch_score<NQB, 2, F16>(a);
+        default: return launch_score<NQB, 1, F16>(a);
     }
-}
-
-// f16 / fp8 index: 1024-thread workgroups, plain loads (the tuned f32 configuration)
-template <int NQB, int KIND>
-static int launch_score_lowp(int U, const ScoreArgs& a) {
-    switch (U) {
-        case 8: return launch_score<NQB, 8, 1024, 0, KIND>(a);
-        case 4: return launch_score<NQB, 4, 1024, 0, KIND>(a);
-        case 2: return launch_score<NQB, 2, 1024, 0, KIND>(a);
-        default: return launch_score<NQB, 1, 1024, 0, KIND>(a);
-    }
-}
-
-template <int NQB>
-static int launch_score_v(const ScanVariant& v, int U, const ScoreArgs& a) {
-    if (v.threads == 1024) return v.nt ? launch_score_u<NQB, 1024, 1>(U, a) : launch_score_u<NQB, 1024, 0>(U, a);
-    return v.nt ? launch_score_u<NQB, 512, 1>(U, a) : launch_score_u<NQB, 512, 0>(U, a);
 }
 
 // Segment schedule knobs (tuning only; results do not depend on them):
@@ -676,18 +636,16 @@ static int cosine_topk_impl(const float* q, int Q, const void* idx, int f16, int
     int32_t* ci = reinterpret_cast<int32_t*>(base + w.id_off);
 
     const int chunks = f16 >= 2 ? D / 64 : (f16 ? D / 32 : D / 16);
-    ScanVariant variant = scan_variant();
-    if (f16) variant.threads = 1024;
-    // loads in flight per lane per group: the largest U <= cap that leaves an EVEN number of groups
+    // loads in flight per lane per group: the largest U <= kScanMaxU that leaves an EVEN number of groups
     // (copy-free ping-pong), else the largest U that divides the row.
     int U = 1;
-    for (int cand = 8; cand >= 1; cand >>= 1)
-        if (cand <= variant.u_cap && chunks % (2 * cand) == 0) { U = cand; break; }
+    for (int cand = kScanMaxU; cand >= 1; cand >>= 1)
+        if (chunks % (2 * cand) == 0) { U = cand; break; }
     if (U == 1 && chunks % 2 != 0)
-        for (int cand = 8; cand >= 1; cand >>= 1)
-            if (cand <= variant.u_cap && chunks % cand == 0) { U = cand; break; }
+        for (int cand = kScanMaxU; cand >= 1; cand >>= 1)
+            if (chunks % cand == 0) { U = cand; break; }
     const int cus = device_cu_count();
-    const int waves_per_block = variant.threads == 1024 ? 16 : 8;
+    const int waves_per_block = kScanThreads / 64;
 
     // 32 queries per pass when their fragments (+ the append counters) fit the 160 KiB of LDS, else 16: at D = 1280 the
     // f32 / f16 / widened-fp8 fragments of 32 queries are exactly 160 KiB and leave no room for the counters
@@ -739,10 +697,10 @@ static int cosine_topk_impl(const float* q, int Q, const void* idx, int f16, int
             ScoreArgs sa{grid, lds, st, qfrag, idx, begin, end, D, qn, row_scale, tau,
                          cs, ci, cnt, w.cap, first ? 1 : 0, capq, gate, nullptr, nullptr};
             if (!gate) timing_kernel_events(kTimeCosineScore, &sa.ev_start, &sa.ev_stop);  // gated launches stay out of the accounts
-            const int rc = f16 == 3 ? (nqb == 1 ? launch_score_lowp<1, 3>(U, sa) : launch_score_lowp<2, 3>(U, sa))
-                           : f16 == 2 ? (nqb == 1 ? launch_score_lowp<1, 2>(U, sa) : launch_score_lowp<2, 2>(U, sa))
-                           : f16  ? (nqb == 1 ? launch_score_lowp<1, 1>(U, sa) : launch_score_lowp<2, 1>(U, sa))
-                                  : (nqb == 1 ? launch_score_v<1>(variant, U, sa) : launch_score_v<2>(variant, U, sa));
+            const int rc = f16 == 3 ? (nqb == 1 ? launch_score_u<1, 3>(U, sa) : launch_score_u<2, 3>(U, sa))
+                           : f16 == 2 ? (nqb == 1 ? launch_score_u<1, 2>(U, sa) : launch_score_u<2, 2>(U, sa))
+                           : f16  ? (nqb == 1 ? launch_score_u<1, 1>(U, sa) : launch_score_u<2, 1>(U, sa))
+                                  : (nqb == 1 ? launch_score_u<1, 0>(U, sa) : launch_score_u<2, 0>(U, sa));
             if (rc != EVI_OK) return rc;
             const int final_pass = end >= N ? 1 : 0;
             hipEvent_t sel_start, sel_stop;

@@ -15,7 +15,6 @@
 #include "common.hpp"
 
 #include <hip/hip_bf16.h>
-#include <stdlib.h>
 
 namespace evi {
 
@@ -70,21 +69,18 @@ __global__ void k_split_weight_long(const float* __restrict__ W, int N, int64_t 
     lo[i] = (__bf16)(x - (float)h);
 }
 
-// MF = 0: v_mfma_f32_32x32x16_bf16 (eight 32x32 accumulators per wave); MF = 1: v_mfma_f32_16x16x32_bf16
-// (thirty-two 16x16 accumulators) — same LDS image, same number of fragment reads and MFMA cycles per
-// k-tile; the chip holds a higher clock on the 16x16 shape (MI355X_MICROARCH.md, DVFS item 7).
 // AH = 1: A is stored as f16 (lda in halves) — an f16 value is exactly hi + lo in bf16, so nothing is lost.
 // AH = 2: A is a bf16 copy of the rows (the "shadow" of an f32 index, = its hi plane): staged without any
 //         conversion; only meaningful with P1 (there is no lo plane to multiply).
 // P1 = 1: single product hi * hi (plain bf16 GEMM: relative error 2^-8 instead of 2^-16) — only for the candidate
 // selection of the many-query top-k, whose results are re-scored exactly; the lo planes are neither loaded,
 // staged nor multiplied.
-// P1 = 2 ("f16x2", opt-in, f32 A only, MF = 0): TWO products on v_mfma_f32_32x32x16_f16 — A = hi + lo with hi = f16(a),
+// P1 = 2 ("f16x2", opt-in, f32 A only): TWO products on v_mfma_f32_32x32x16_f16 — A = hi + lo with hi = f16(a),
 // lo = f16(a - hi) (22 significant bits), W rounded ONCE to f16 (2^-12 relative per weight; `Whi` then holds f16 bits,
 // there is no W lo plane).  Two thirds of the MFMA work of the three-product form; the error is the weights' f16 rounding —
 // four times finer than the TF32 rounding of BOTH operands the reference runs with on CUDA
 // (configs/extras/default.yaml:11) — and f16's range: |a|, |w| must stay below 65 504.
-template <int ACT, int MF, int AH = 0, int P1 = 0>
+template <int ACT, int AH = 0, int P1 = 0>
 __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
     const float* __restrict__ A, int64_t M, int K, int64_t lda, const __bf16* __restrict__ Whi,
     const __bf16* __restrict__ Wlo, int N, int Kp, const float* __restrict__ bias, float* __restrict__ C,
@@ -105,7 +101,7 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
     if (bt.count > 0) Kp = (K + XK - 1) / XK * XK;
     constexpr bool kALo = P1 != 1;  // A lo plane staged and multiplied (three-product and f16x2 forms)
     constexpr bool kWLo = P1 == 0;  // W lo plane (three-product form only)
-    static_assert(P1 != 2 || (AH == 0 && MF == 0), "f16x2 takes f32 A and the 32x32x16 MFMA");
+    static_assert(P1 != 2 || AH == 0, "f16x2 takes f32 A");
     __shared__ uint4 sAhi[2][XM * 4], sWhi[2][XN * 4];                                     // 2 stages x 16 KiB each
     __shared__ uint4 sAlo[kALo ? 2 : 1][kALo ? XM * 4 : 1], sWlo[kWLo ? 2 : 1][kWLo ? XN * 4 : 1];  // lo planes where the form has them
     const int tid = threadIdx.x;
@@ -239,24 +235,15 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
         if (kWLo) *reinterpret_cast<u32x4*>(&sWlo[kWLo ? buf : 0][kWLo ? slot3(r, c) : 0]) = ok ? rwl[set][i] : zero16;
     };
 
-    f32x16 acc[MF ? 1 : 4][MF ? 1 : 2];   // MF = 0
-    f32x4 acc16[MF ? 8 : 1][MF ? 4 : 1];  // MF = 1
-    if (MF) {
+    f32x16 acc[4][2];
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc16[MF ? i : 0][MF ? j : 0] = f32x4{0.f, 0.f, 0.f, 0.f};
-    } else {
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[MF ? 0 : i][MF ? 0 : j][r] = 0.f;
-    }
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    const int fr = lane & 31, fh = lane >> 5;    // 32x32x16 fragment coordinates
-    const int r16 = lane & 15, q16 = lane >> 4;  // 16x16x32 fragment coordinates
+    const int fr = lane & 31, fh = lane >> 5;  // 32x32x16 fragment coordinates
     // Two LDS stages: stage `cur` is multiplied while the next tile (already in registers) is split and
     // written to the other stage piece by piece and the tile after it is fetched into the freed
     // registers; one barrier per k-tile.
@@ -293,25 +280,24 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
         const int k0 = kbase + u * XK;
         const int cur = NS == 2 ? u : cur_rt;           // LDS stage holding tile k0
         const int set = NS == 2 ? (u ^ 1) : 0;          // staging set holding tile k0 + XK
-        // Eight MFMA groups per k-tile: (MF = 0) two 16-wide k-steps x four 32-row blocks, six MFMAs each;
-        // (MF = 1) eight 16-row blocks over the whole 32-wide k-tile, twelve MFMAs each.  The A fragments of
+        // Eight MFMA groups per k-tile: two 16-wide k-steps x four 32-row blocks, six MFMAs each.  The A fragments of
         // group g + 1 are read from LDS before group g's MFMAs are issued (ping-pong registers), so an MFMA
         // never waits on the LDS latency of its own operands.
         // A fragments are read AHEAD groups before their MFMAs: one group (six MFMAs = 192 cycles) covers the LDS
         // latency when three products are multiplied; with one product a group is two MFMAs, so read two ahead.
         constexpr int AHEAD = P1 == 1 ? 2 : 1, RING = AHEAD + 1;
-        bf16x8 fah[RING], fal[RING], fbh[MF ? 1 : 2][MF ? 4 : 2], fbl[MF ? 1 : 2][MF ? 4 : 2];
+        bf16x8 fah[RING], fal[RING], fbh[2][2], fbl[2][2];
         auto read_a = [&](int g) {
-            const int c = MF ? q16 : ((g >> 2) << 1) + fh;  // MF = 0: chunk holding k = 16 (g >> 2) + 8 h .. + 7
-            const int row = MF ? wm * 128 + g * 16 + r16 : wm * 128 + (g & 3) * 32 + fr;
+            const int c = ((g >> 2) << 1) + fh;  // chunk holding k = 16 (g >> 2) + 8 h .. + 7
+            const int row = wm * 128 + (g & 3) * 32 + fr;
             fah[g % RING] = *reinterpret_cast<const bf16x8*>(&sAhi[cur][slot3(row, c)]);
             if (kALo) fal[g % RING] = *reinterpret_cast<const bf16x8*>(&sAlo[kALo ? cur : 0][kALo ? slot3(row, c) : 0]);
         };
         auto read_b = [&](int ks) {
-            const int c = MF ? q16 : (ks << 1) + fh;
+            const int c = (ks << 1) + fh;
 #pragma unroll
-            for (int j = 0; j < (MF ? 4 : 2); ++j) {
-                const int row = MF ? wn * 64 + j * 16 + r16 : wn * 64 + j * 32 + fr;
+            for (int j = 0; j < 2; ++j) {
+                const int row = wn * 64 + j * 32 + fr;
                 fbh[ks][j] = *reinterpret_cast<const bf16x8*>(&sWhi[cur][slot3(row, c)]);
                 if (kWLo) fbl[ks][j] = *reinterpret_cast<const bf16x8*>(&sWlo[kWLo ? cur : 0][kWLo ? slot3(row, c) : 0]);
             }
@@ -322,31 +308,21 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
             if (g + AHEAD < 8) read_a(g + AHEAD);
-            if (!MF && g == 2) read_b(1);
-            if (MF) {
+            if (g == 2) read_b(1);
+            const int i = g & 3, ks = g >> 2;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    f32x4& c = acc16[MF ? g : 0][MF ? j : 0];
-                    if (!P1) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fal[g % RING], fbh[0][MF ? j : 0], c, 0, 0, 0);
-                    if (!P1) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fah[g % RING], fbl[0][MF ? j : 0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fah[g % RING], fbh[0][MF ? j : 0], c, 0, 0, 0);
+            for (int j = 0; j < 2; ++j) {
+                f32x16& c = acc[i][j];
+                if (P1 == 2) {  // f16x2: (lo + hi) * W on the f16 instruction, the small term first
+                    typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
+                    const f16x8v wv = __builtin_bit_cast(f16x8v, fbh[ks][j]);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, fal[g % RING]), wv, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, fah[g % RING]), wv, c, 0, 0, 0);
+                    continue;
                 }
-            } else {
-                const int i = g & 3, ks = g >> 2;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    f32x16& c = acc[MF ? 0 : i][MF ? 0 : j];
-                    if (P1 == 2) {  // f16x2: (lo + hi) * W on the f16 instruction, the small term first
-                        typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
-                        const f16x8v wv = __builtin_bit_cast(f16x8v, fbh[MF ? 0 : ks][MF ? 0 : j]);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, fal[g % RING]), wv, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, fah[g % RING]), wv, c, 0, 0, 0);
-                        continue;
-                    }
-                    if (!P1) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal[g % RING], fbh[MF ? 0 : ks][MF ? 0 : j], c, 0, 0, 0);
-                    if (!P1) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah[g % RING], fbl[MF ? 0 : ks][MF ? 0 : j], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah[g % RING], fbh[MF ? 0 : ks][MF ? 0 : j], c, 0, 0, 0);
-                }
+                if (!P1) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal[g % RING], fbh[ks][j], c, 0, 0, 0);
+                if (!P1) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah[g % RING], fbl[ks][j], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah[g % RING], fbh[ks][j], c, 0, 0, 0);
             }
             // one staging piece in the shadow of this group's MFMAs (pieces 0-3: A, 4-5: W).  Past the last
             // tile the pieces move zeros into a stage nobody reads: cheaper than a branch in this loop.
@@ -374,7 +350,7 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
       }
     }
 
-    if (ACT == 3) {  // threshold filter instead of a store (MF = 0 layout): survivors are rare after the first slab
+    if (ACT == 3) {  // threshold filter instead of a store: survivors are rare after the first slab
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int n = n0 + wn * 64 + j * 32 + fr;
@@ -386,7 +362,7 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
                 for (int r = 0; r < 16; ++r) {
                     const int64_t m = m0 + wm * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
                     if (m >= M) continue;
-                    float sc = acc[MF ? 0 : i][MF ? 0 : j][r];
+                    float sc = acc[i][j][r];
                     if (flt.row_scale) sc *= flt.row_scale[flt.row0 + m];
                     if (sc >= t || sc != sc) {
                         const int32_t pos = atomicAdd(&flt.cand_cnt[n * flt.cnt_stride], 1);
@@ -397,23 +373,6 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
                             atomicOr(flt.status, 2);
                         }
                     }
-                }
-        }
-        return;
-    }
-    if (MF) {  // 16x16 accumulators: col = lane & 15, row = 4 (lane >> 4) + r
-        const bool interior = m0 + XM <= M && n0 + XN <= N;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + j * 16 + r16;
-            if (!interior && n >= N) continue;
-            const float bv = bias ? bias[n] : 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int64_t m = m0 + wm * 128 + i * 16 + q16 * 4 + r;
-                    if (interior || m < M) C[m * ldc + n] = act3(acc16[MF ? i : 0][MF ? j : 0][r] + bv, ACT);
                 }
         }
         return;
@@ -473,7 +432,7 @@ int launch_gemm_bf16_presplit(const void* A, int a_f16, int single, int64_t M, i
     const GemmFilter flt{};
     const int tok = timing_begin(kTimeGemm, st);
 #define EVI_LAUNCH_PS(AHV, P1V)                                                                                          \
-    hipLaunchKernelGGL((k_gemm_nt_bf16x3<0, 0, AHV, P1V>), grid, dim3(kXThreads), 0, st, static_cast<const float*>(A), M, K, lda, \
+    hipLaunchKernelGGL((k_gemm_nt_bf16x3<0, AHV, P1V>), grid, dim3(kXThreads), 0, st, static_cast<const float*>(A), M, K, lda, \
                        hi, lo, N, Kp, static_cast<const float*>(nullptr), C, ldc, flt, GemmBatch{})
     if (a_f16 == 2) EVI_LAUNCH_PS(2, 1);
     else if (a_f16 && single) EVI_LAUNCH_PS(1, 1);
@@ -495,7 +454,7 @@ int launch_gemm_bf16x3_filter(const void* A, int a_f16, int single, int64_t M, i
     const dim3 grid((unsigned)(((M + XM - 1) / XM) * ((N + XN - 1) / XN)));
     const int tok = timing_begin(kTimeGemm, st);
 #define EVI_LAUNCH_FL(AHV, P1V)                                                                                          \
-    hipLaunchKernelGGL((k_gemm_nt_bf16x3<3, 0, AHV, P1V>), grid, dim3(kXThreads), 0, st, static_cast<const float*>(A), M, K, lda, \
+    hipLaunchKernelGGL((k_gemm_nt_bf16x3<3, AHV, P1V>), grid, dim3(kXThreads), 0, st, static_cast<const float*>(A), M, K, lda, \
                        hi, lo, N, Kp, static_cast<const float*>(nullptr), static_cast<float*>(nullptr), (int64_t)0, flt, GemmBatch{})
     if (a_f16 == 2) EVI_LAUNCH_FL(2, 1);
     else if (a_f16 && single) EVI_LAUNCH_FL(1, 1);
@@ -540,21 +499,13 @@ int launch_gemm_nt_bf16x3_wplanes(const float* A, int64_t M, int K, int64_t lda,
     const GemmFilter flt{};
     const dim3 grid((unsigned)(((M + XM - 1) / XM) * ((N + XN - 1) / XN)));
     const int tok = timing_begin(kTimeGemm, st);
-    // EVI_GEMM_MFMA=16 selects the 16x16x32 form (tuning knob; measured 3-10 % slower here: its stores are 64-byte
-    // segments and the clock advantage of the shape does not make up for it)
-    static const bool mfma16 = [] {
-        const char* e = getenv("EVI_GEMM_MFMA");
-        return e && e[0] == '1';
-    }();
 #define EVI_LAUNCH_X3(ACT)                                                                                              \
     if (single == 2)                                                                                                    \
-        hipLaunchKernelGGL((k_gemm_nt_bf16x3<ACT, 0, 0, 2>), grid, dim3(kXThreads), 0, st, A, M, K, lda, hi, lo, N, Kp, bias, C, ldc, flt, plain); \
+        hipLaunchKernelGGL((k_gemm_nt_bf16x3<ACT, 0, 2>), grid, dim3(kXThreads), 0, st, A, M, K, lda, hi, lo, N, Kp, bias, C, ldc, flt, plain); \
     else if (single)                                                                                                    \
-        hipLaunchKernelGGL((k_gemm_nt_bf16x3<ACT, 0, 0, 1>), grid, dim3(kXThreads), 0, st, A, M, K, lda, hi, lo, N, Kp, bias, C, ldc, flt, plain); \
-    else if (mfma16)                                                                                                    \
-        hipLaunchKernelGGL((k_gemm_nt_bf16x3<ACT, 1>), grid, dim3(kXThreads), 0, st, A, M, K, lda, hi, lo, N, Kp, bias, C, ldc, flt, plain); \
+        hipLaunchKernelGGL((k_gemm_nt_bf16x3<ACT, 0, 1>), grid, dim3(kXThreads), 0, st, A, M, K, lda, hi, lo, N, Kp, bias, C, ldc, flt, plain); \
     else                                                                                                                \
-        hipLaunchKernelGGL((k_gemm_nt_bf16x3<ACT, 0>), grid, dim3(kXThreads), 0, st, A, M, K, lda, hi, lo, N, Kp, bias, C, ldc, flt, plain);
+        hipLaunchKernelGGL((k_gemm_nt_bf16x3<ACT>), grid, dim3(kXThreads), 0, st, A, M, K, lda, hi, lo, N, Kp, bias, C, ldc, flt, plain);
     switch (act) {
         case 1: EVI_LAUNCH_X3(1) break;
         case 2: EVI_LAUNCH_X3(2) break;
@@ -588,7 +539,7 @@ int launch_gemm_nt_bf16x3_splitk(const float* A, int64_t M, int64_t Ktot, int64_
     bt.w_ld = Kp_tot;
     const dim3 grid((unsigned)(((M + XM - 1) / XM) * ((N + XN - 1) / XN)), (unsigned)S);
     const int tok = timing_begin(kTimeGemm, st);
-    hipLaunchKernelGGL((k_gemm_nt_bf16x3<0, 0>), grid, dim3(kXThreads), 0, st, A, M, Ks, lda, hi, lo, N, Ks, static_cast<const float*>(nullptr),
+    hipLaunchKernelGGL((k_gemm_nt_bf16x3<0>), grid, dim3(kXThreads), 0, st, A, M, Ks, lda, hi, lo, N, Ks, static_cast<const float*>(nullptr),
                        Cparts, (int64_t)N, flt, bt);
     timing_end(tok, st);
     EVI_LAUNCH_CHECK();

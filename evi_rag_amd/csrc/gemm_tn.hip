@@ -199,9 +199,8 @@ int launch_gemm_tn_bf16x3(const float* A, int64_t lda, int M, const float* B, in
     if (M <= 0 || N <= 0 || S <= 0) return EVI_OK;
     const dim3 grid((unsigned)(((M + TM - 1) / TM) * ((N + TNN - 1) / TNN) * S));
     const int tok = timing_begin(kTimeGemm, st);
-    // 8-byte staging loads when every column pair is aligned and inside the operands (EVI_TN_V2=0: the 4-byte form, for A/B runs)
-    static const bool v2_ok = [] { const char* e = getenv("EVI_TN_V2"); return !(e && e[0] == '0'); }();
-    const bool v2 = v2_ok && M >= 2 && N >= 2 && M % 2 == 0 && N % 2 == 0 && lda % 2 == 0 && ldb % 2 == 0 &&
+    // 8-byte staging loads when every column pair is aligned and inside the operands, else the 4-byte form
+    const bool v2 = M >= 2 && N >= 2 && M % 2 == 0 && N % 2 == 0 && lda % 2 == 0 && ldb % 2 == 0 &&
                     (reinterpret_cast<uintptr_t>(A) & 7) == 0 && (reinterpret_cast<uintptr_t>(B) & 7) == 0;
     if (single && v2) hipLaunchKernelGGL((k_gemm_tn_bf16x3<1, 1>), grid, dim3(kTThreads), 0, st, A, lda, M, B, ldb, N, K, Ks, Cparts);
     else if (single) hipLaunchKernelGGL((k_gemm_tn_bf16x3<1, 0>), grid, dim3(kTThreads), 0, st, A, lda, M, B, ldb, N, K, Ks, Cparts);

@@ -11,10 +11,11 @@
 // Graphs in a batch are independent and small (N_g ~ 10^3, E_g ~ 10^3..10^5).  All kernels are HBM/L2-latency-bound
 // integer and gather work; algorithmic bytes per DDE round = E*(4 nbr + C*4 gather) + N*(8 rowptr + C*4 write)
 // (SURVEY.md §8d).  The reference's batch is 32 graphs, so "one workgroup per graph" leaves 7/8 of the chip idle:
-//   * the CSR is a counting sort whose counters live in LDS (global atomics run at the memory side, ~20 G/s scattered);
-//     a graph's edge list is cut into P parts (P = 8 at 32 graphs, 1 from 512 graphs on), every part counts and fills from
-//     its own LDS counters, and a per-graph scan in between turns the P x N_g partial counts into row pointers and
-//     per-part cursors — B x P workgroups, no global atomics, no per-level barriers of 1024 threads;
+//   * the CSR is a counting sort in ONE launch of one workgroup per (graph, side) (k_graph_csr_side): the side's row
+//     counters AND its (nbr, eid) arrays are staged in LDS, scattered into with ds atomics (global atomics run at the
+//     memory side, ~20 G/s scattered) and written out once, coalesced.  A graph beyond the LDS budget is built whole by
+//     its side-0 workgroup with its counters in the global workspace: 2 * max(N, 1) int32, which is all that
+//     evi_graph_csr_workspace_bytes asks for (8 B per node; it asked 64 B per node while an 8-part build existed);
 //   * DDE is node-parallel over the WHOLE batch: one thread per (node, chain) — the forward chain walks in-rows, the
 //     reverse chain out-rows, both are independent given the previous round — and one launch per round pair instead of
 //     workgroup barriers, so a round is one row gather deep whatever the batch size.  Long rows (power-law hubs) are
@@ -32,8 +33,6 @@ namespace evi {
 
 constexpr int kGraphThreads = 1024;
 constexpr int kHubDegree = 32;
-constexpr int kHubListCap = 4096;
-constexpr int kCsrMaxParts = 8;  // edge-list parts per graph of the small-batch CSR build
 
 // ---- edge -> graph assignment -----------------------------------------------------------------
 // status bits: 1 = head outside [ptr[0], ptr[B]), 2 = head/tail in different graphs,
@@ -93,13 +92,6 @@ __global__ void k_edge_near_mask(const int64_t* __restrict__ edge_index, int64_t
 }
 
 // ---- CSR ------------------------------------------------------------------------------------------
-struct GraphShared {
-    int scan[kGraphThreads];
-    int hubs[kHubListCap];
-    int hub_count;
-    int carry;
-};
-
 // Exclusive scan of cnt[0..n1-n0) (one counter per node of the graph) into ptr[n0..n1) (+ base);
 // ptr[n1] = base + total.  All threads call.  Wave-level shuffles scan 64 counters at a time, the 16 wave totals go
 // through LDS: two barriers per 1024 nodes instead of the twenty of a log-step LDS scan.
@@ -145,9 +137,8 @@ __device__ inline void block_exclusive_scan(Sh& sh, const int32_t* cnt, int32_t*
     block_exclusive_scan_fn(sh, [&](int i) { return cnt[i]; }, ptr, n0, n1, base);
 }
 
-// Counting-sort CSR of one graph.  cin / cout are the per-node counters, indexed by LOCAL node id: in
-// LDS when the graph's 2 * N_g counters fit the launch's dynamic LDS (ds_add_rtn instead of L2 atomics),
-// else in the global workspace.
+// Counting-sort CSR of one graph with its per-node counters cin / cout (indexed by LOCAL node id) in the global
+// workspace: the build of the graphs that exceed k_graph_csr_side's LDS budget.
 template <class Sh>
 __device__ inline void csr_build(Sh& sh, const int64_t* __restrict__ edge_index, int64_t E, int64_t n0,
                                  int64_t n1, int64_t e0, int64_t e1, int32_t* cin, int32_t* cout,
@@ -182,24 +173,6 @@ __device__ inline void csr_build(Sh& sh, const int64_t* __restrict__ edge_index,
         out_nbr[po] = (int32_t)d;
         out_eid[po] = (int32_t)e;
     }
-}
-
-__global__ __launch_bounds__(kGraphThreads) void k_graph_csr(
-    const int64_t* __restrict__ edge_index, int64_t E, const int64_t* __restrict__ node_ptr,
-    const int64_t* __restrict__ edge_ptr, int32_t* __restrict__ in_ptr, int32_t* __restrict__ in_nbr,
-    int32_t* __restrict__ in_eid, int32_t* __restrict__ out_ptr, int32_t* __restrict__ out_nbr,
-    int32_t* __restrict__ out_eid, int32_t* __restrict__ cnt_in, int32_t* __restrict__ cnt_out, int lds_nodes) {
-    __shared__ GraphShared sh;
-    extern __shared__ int32_t lds_cnt[];  // [2 * lds_nodes]
-    const int g = blockIdx.x;
-    const int64_t n0 = node_ptr[g], n1 = node_ptr[g + 1];
-    const int64_t e0 = edge_ptr[g], e1 = edge_ptr[g + 1];
-    if (n1 - n0 <= lds_nodes)
-        csr_build(sh, edge_index, E, n0, n1, e0, e1, lds_cnt, lds_cnt + lds_nodes, in_ptr, in_nbr, in_eid, out_ptr,
-                  out_nbr, out_eid);
-    else
-        csr_build(sh, edge_index, E, n0, n1, e0, e1, cnt_in + n0, cnt_out + n0, in_ptr, in_nbr, in_eid, out_ptr, out_nbr,
-                  out_eid);
 }
 
 // ---- CSR with the output staged in LDS: one workgroup per (graph, side) ---------------------------------------
@@ -296,158 +269,6 @@ __global__ __launch_bounds__(kGraphThreads) void k_graph_csr_side(
     for (int i = tid; i < total; i += kGraphThreads) {
         nbr[e0 + i] = s_nbr[i];
         eid[e0 + i] = s_eid[i];
-    }
-}
-
-// ---- CSR in P parts per graph (small batches) ------------------------------------------------------------
-// part counts / cursors: [2][P][N] int32 in the workspace (in-counters first, out-counters second), part-major: the count
-// and fill kernels of part p stream their own [N_g] slice, the scan kernel reads P coalesced streams.
-__device__ inline void part_range(int64_t e0, int64_t e1, int P, int p, int64_t& b, int64_t& e) {
-    const int64_t len = e1 - e0;
-    b = e0 + len * p / P;
-    e = e0 + len * (p + 1) / P;
-}
-
-// A: count the part's edges per node in LDS, publish the partial counts.
-__global__ __launch_bounds__(kGraphThreads) void k_csr_part_count(
-    const int64_t* __restrict__ edge_index, int64_t E, const int64_t* __restrict__ node_ptr,
-    const int64_t* __restrict__ edge_ptr, int64_t N, int P, int32_t* __restrict__ part, int lds_nodes) {
-    extern __shared__ int32_t lds_cnt[];  // [2 * lds_nodes]
-    const int g = blockIdx.x / P, p = blockIdx.x % P, tid = threadIdx.x;
-    const int64_t n0 = node_ptr[g], n1 = node_ptr[g + 1];
-    const int ng = (int)(n1 - n0);
-    if (ng > lds_nodes) return;  // oversize graph: k_csr_part_scan builds it whole (global counters)
-    int32_t* cin = lds_cnt;
-    int32_t* cout = lds_cnt + lds_nodes;
-    for (int v = tid; v < ng; v += kGraphThreads) cin[v] = cout[v] = 0;
-    __syncthreads();
-    int64_t b, e;
-    part_range(edge_ptr[g], edge_ptr[g + 1], P, p, b, e);
-    for (int64_t i = b + tid; i < e; i += kGraphThreads) {
-        const int64_t s = edge_index[i], d = edge_index[E + i];
-        if (s < n0 || s >= n1 || d < n0 || d >= n1) continue;
-        atomicAdd(&cin[d - n0], 1);
-        atomicAdd(&cout[s - n0], 1);
-    }
-    __syncthreads();
-    int32_t* pin = part + (int64_t)p * N + n0;
-    int32_t* pout = part + ((int64_t)P + p) * N + n0;
-    for (int v = tid; v < ng; v += kGraphThreads) {
-        pin[v] = cin[v];
-        pout[v] = cout[v];
-    }
-}
-
-// B: one workgroup per graph: row pointers from the summed partial counts; the partial counts become each part's first
-// write position of the row.  Graphs too large for the parts' LDS counters are built here in one piece (legacy path).
-__global__ __launch_bounds__(kGraphThreads) void k_csr_part_scan(
-    const int64_t* __restrict__ edge_index, int64_t E, const int64_t* __restrict__ node_ptr,
-    const int64_t* __restrict__ edge_ptr, int64_t N, int P, int32_t* __restrict__ part, int32_t* __restrict__ in_ptr,
-    int32_t* __restrict__ in_nbr, int32_t* __restrict__ in_eid, int32_t* __restrict__ out_ptr,
-    int32_t* __restrict__ out_nbr, int32_t* __restrict__ out_eid, int lds_nodes) {
-    __shared__ GraphShared sh;
-    const int g = blockIdx.x, tid = threadIdx.x;
-    const int64_t n0 = node_ptr[g], n1 = node_ptr[g + 1];
-    const int64_t e0 = edge_ptr[g], e1 = edge_ptr[g + 1];
-    const int ng = (int)(n1 - n0);
-    if (ng > lds_nodes) {  // the graph's slices of parts 0 of `part` serve as its global counters
-        csr_build(sh, edge_index, E, n0, n1, e0, e1, part + n0, part + (int64_t)P * N + n0, in_ptr, in_nbr, in_eid, out_ptr,
-                  out_nbr, out_eid);
-        return;
-    }
-    // Both halves in ONE pass: a node's in- and out-totals ride in the two halves of a 64-bit word through the same
-    // wave / workgroup scan (each sum stays below 2^31, so no carry crosses), and the part cursors are written from the
-    // registers that still hold the part counts — per 1024 nodes: 2 P independent loads, one scan, two barriers.
-    int32_t* pci = part + n0;                       // + q * N + v
-    int32_t* pco = part + (int64_t)P * N + n0;
-    unsigned long long* wsum = reinterpret_cast<unsigned long long*>(sh.scan);
-    const int lane = tid & 63, wave = tid >> 6;
-    unsigned long long carry = (unsigned long long)(uint32_t)e0 | ((unsigned long long)(uint32_t)e0 << 32);
-    for (int v0 = 0; v0 < ng; v0 += kGraphThreads) {
-        const int v = v0 + tid;
-        const bool live = v < ng;
-        int ci[kCsrMaxParts], co[kCsrMaxParts];
-#pragma unroll
-        for (int q = 0; q < kCsrMaxParts; ++q) {
-            ci[q] = (live && q < P) ? pci[(int64_t)q * N + v] : 0;
-            co[q] = (live && q < P) ? pco[(int64_t)q * N + v] : 0;
-        }
-        unsigned int ti = 0, to = 0;
-#pragma unroll
-        for (int q = 0; q < kCsrMaxParts; ++q) {
-            ti += (unsigned)ci[q];
-            to += (unsigned)co[q];
-        }
-        const unsigned long long val = (unsigned long long)ti | ((unsigned long long)to << 32);
-        unsigned long long incl = val;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned long long up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        unsigned long long before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kGraphThreads / 64; ++w) {
-            const unsigned long long t = wsum[w];
-            if (w < wave) before += t;
-            total += t;
-        }
-        const unsigned long long mine = carry + before + incl - val;
-        if (live) {
-            int run_i = (int)(uint32_t)mine, run_o = (int)(uint32_t)(mine >> 32);
-            in_ptr[n0 + v] = run_i;
-            out_ptr[n0 + v] = run_o;
-#pragma unroll
-            for (int q = 0; q < kCsrMaxParts; ++q)
-                if (q < P) {
-                    pci[(int64_t)q * N + v] = run_i;
-                    pco[(int64_t)q * N + v] = run_o;
-                    run_i += ci[q];
-                    run_o += co[q];
-                }
-        }
-        carry += total;
-        __syncthreads();  // wsum is rewritten by the next chunk
-    }
-    if (tid == 0) {
-        in_ptr[n1] = (int)(uint32_t)carry;
-        out_ptr[n1] = (int)(uint32_t)(carry >> 32);
-    }
-}
-
-// C: every part scatters its edges from its own cursors (LDS).
-__global__ __launch_bounds__(kGraphThreads) void k_csr_part_fill(
-    const int64_t* __restrict__ edge_index, int64_t E, const int64_t* __restrict__ node_ptr,
-    const int64_t* __restrict__ edge_ptr, int64_t N, int P, const int32_t* __restrict__ part,
-    int32_t* __restrict__ in_nbr, int32_t* __restrict__ in_eid, int32_t* __restrict__ out_nbr,
-    int32_t* __restrict__ out_eid, int lds_nodes) {
-    extern __shared__ int32_t lds_cnt[];
-    const int g = blockIdx.x / P, p = blockIdx.x % P, tid = threadIdx.x;
-    const int64_t n0 = node_ptr[g], n1 = node_ptr[g + 1];
-    const int ng = (int)(n1 - n0);
-    if (ng > lds_nodes) return;
-    int32_t* cin = lds_cnt;
-    int32_t* cout = lds_cnt + lds_nodes;
-    const int32_t* pin = part + (int64_t)p * N + n0;
-    const int32_t* pout = part + ((int64_t)P + p) * N + n0;
-    for (int v = tid; v < ng; v += kGraphThreads) {
-        cin[v] = pin[v];
-        cout[v] = pout[v];
-    }
-    __syncthreads();
-    int64_t b, e;
-    part_range(edge_ptr[g], edge_ptr[g + 1], P, p, b, e);
-    for (int64_t i = b + tid; i < e; i += kGraphThreads) {
-        const int64_t s = edge_index[i], d = edge_index[E + i];
-        if (s < n0 || s >= n1 || d < n0 || d >= n1) continue;
-        const int pi = atomicAdd(&cin[d - n0], 1);
-        in_nbr[pi] = (int32_t)s;
-        in_eid[pi] = (int32_t)i;
-        const int po = atomicAdd(&cout[s - n0], 1);
-        out_nbr[po] = (int32_t)d;
-        out_eid[po] = (int32_t)i;
     }
 }
 
@@ -856,21 +677,9 @@ extern "C" int evi_qa_edge_mask(const int64_t* edge_index, int64_t E, int64_t nu
     return EVI_OK;
 }
 
-constexpr int kCsrLdsNodes = 6144;  // 48 KiB of dynamic LDS: the counters of graphs up to 6144 nodes stay on chip
-
-// parts per graph: enough workgroups to cover the chip twice at small batches, one from 512 graphs on
-static int csr_parts(int B) {
-    int P = 1;
-    while (P < kCsrMaxParts && (int64_t)B * P * 2 <= 512) P <<= 1;
-    if (const char* e = getenv("EVI_CSR_PARTS")) {  // tuning / tests: force the number of parts (1, 2, 4, 8)
-        const int v = atoi(e);
-        if (v == 1 || v == 2 || v == 4 || v == 8) P = v;
-    }
-    return P;
-}
-
+// the in- and out-counters of graphs beyond k_graph_csr_side's LDS budget
 extern "C" size_t evi_graph_csr_workspace_bytes(int64_t N) {
-    return (size_t)(N > 0 ? N : 1) * 2 * kCsrMaxParts * sizeof(int32_t);
+    return (size_t)(N > 0 ? N : 1) * 2 * sizeof(int32_t);
 }
 
 extern "C" int evi_graph_csr(const int64_t* edge_index, int64_t E, const int64_t* node_ptr,
@@ -886,45 +695,18 @@ extern "C" int evi_graph_csr(const int64_t* edge_index, int64_t E, const int64_t
         return fail(EVI_ERR_NOMEM, "evi_graph_csr: workspace %zu B < %zu B", workspace_bytes,
                     evi_graph_csr_workspace_bytes(N));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int P = csr_parts(B);
-    const size_t lds = 2 * kCsrLdsNodes * sizeof(int32_t);
-    // default: the LDS-staged build, one workgroup per (graph, side) in ONE launch; EVI_CSR_BUILD=parts selects the older
-    // global-scatter kernels (A/B runs, and the path graphs beyond the LDS budget take inside the new kernel anyway)
-    static const bool staged = [] {
-        const char* e = getenv("EVI_CSR_BUILD");
-        return !(e && e[0] == 'p');
-    }();
-    if (staged && !getenv("EVI_CSR_PARTS")) {
-        static thread_local bool attr = false;
-        const size_t side_lds = (size_t)(kCsrSideNodes + 2 * kCsrSideEdges) * sizeof(int32_t);
-        if (!attr) {
-            EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_graph_csr_side),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)side_lds));
-            attr = true;
-        }
-        int32_t* cnt_in = static_cast<int32_t*>(workspace);
-        int32_t* cnt_out = cnt_in + (N > 0 ? N : 1);
-        const unsigned grid = (unsigned)((B + 7) / 8 * 16);
-        hipLaunchKernelGGL(k_graph_csr_side, dim3(grid), dim3(kGraphThreads), side_lds, st, edge_index, E, node_ptr, edge_ptr, B,
-                           in_ptr, in_nbr, in_eid, out_ptr, out_nbr, out_eid, cnt_in, cnt_out);
-        EVI_LAUNCH_CHECK();
-        return EVI_OK;
+    static thread_local bool attr = false;
+    const size_t side_lds = (size_t)(kCsrSideNodes + 2 * kCsrSideEdges) * sizeof(int32_t);
+    if (!attr) {
+        EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_graph_csr_side),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)side_lds));
+        attr = true;
     }
-    if (P == 1) {
-        int32_t* cnt_in = static_cast<int32_t*>(workspace);
-        int32_t* cnt_out = cnt_in + (N > 0 ? N : 1);
-        hipLaunchKernelGGL(k_graph_csr, dim3(B), dim3(kGraphThreads), lds, st, edge_index, E, node_ptr, edge_ptr, in_ptr, in_nbr,
-                           in_eid, out_ptr, out_nbr, out_eid, cnt_in, cnt_out, kCsrLdsNodes);
-    } else {
-        int32_t* part = static_cast<int32_t*>(workspace);  // [2][N][P]
-        const int64_t Nn = N > 0 ? N : 1;
-        hipLaunchKernelGGL(k_csr_part_count, dim3(B * P), dim3(kGraphThreads), lds, st, edge_index, E, node_ptr, edge_ptr, Nn, P,
-                           part, kCsrLdsNodes);
-        hipLaunchKernelGGL(k_csr_part_scan, dim3(B), dim3(kGraphThreads), 0, st, edge_index, E, node_ptr, edge_ptr, Nn, P, part,
-                           in_ptr, in_nbr, in_eid, out_ptr, out_nbr, out_eid, kCsrLdsNodes);
-        hipLaunchKernelGGL(k_csr_part_fill, dim3(B * P), dim3(kGraphThreads), lds, st, edge_index, E, node_ptr, edge_ptr, Nn, P,
-                           (const int32_t*)part, in_nbr, in_eid, out_nbr, out_eid, kCsrLdsNodes);
-    }
+    int32_t* cnt_in = static_cast<int32_t*>(workspace);
+    int32_t* cnt_out = cnt_in + (N > 0 ? N : 1);
+    const unsigned grid = (unsigned)((B + 7) / 8 * 16);
+    hipLaunchKernelGGL(k_graph_csr_side, dim3(grid), dim3(kGraphThreads), side_lds, st, edge_index, E, node_ptr, edge_ptr, B,
+                       in_ptr, in_nbr, in_eid, out_ptr, out_nbr, out_eid, cnt_in, cnt_out);
     EVI_LAUNCH_CHECK();
     return EVI_OK;
 }

@@ -748,7 +748,9 @@ static FwdLayout fwd_layout(int64_t N, int64_t E, int B, int D, int H, int F, in
     const size_t f = sizeof(float);
     L.rel_first = m.take(L.dedupe ? (size_t)R * 4 : 256);
     L.status = m.take(256);
-    L.csr_ws = m.take(evi_graph_csr_workspace_bytes(N));
+    // evi_graph_csr uses the first evi_graph_csr_workspace_bytes(N) = 8 B per node; the region keeps the 64 B per node it
+    // had when the retriever layouts were pinned (tests/test_library_abi.py), so no later field moves
+    L.csr_ws = m.take((size_t)(N > 0 ? N : 1) * 64);
     L.wts = place_weight_derived(m, D, H, F);
     L.wsplit = m.take(gemm_bf16x3_workspace_bytes(H > D ? H : D, H > D ? H : D));
     L.P = m.take((size_t)L.ec * D * f);

@@ -322,12 +322,13 @@ int evi_qa_edge_mask(const int64_t* edge_index, int64_t E, int64_t num_nodes, co
 
 /* ---- G1: adjacency as CSR ------------------------------------------------------------------- */
 
-/* In-edge and out-edge CSR of every graph of the batch (one workgroup per graph).  Row v of the
+/* In-edge and out-edge CSR of every graph of the batch (one launch, one workgroup per graph and side).  Row v of the
  * in-CSR lists (source node, edge id) of the edges u -> v; the out-CSR lists (target, edge id) of
  * v -> w.  Together they are the undirected adjacency of _build_undirected_adjacency
  * (scripts/build_retrieval_pipeline.py:570-586); self loops appear once in each half.  Node and
  * edge ids are batch-global int32; the order inside a row is unspecified.
- *   *_ptr [N+1] i32, *_nbr [E] i32, *_eid [E] i32; workspace: evi_graph_csr_workspace_bytes(N). */
+ *   *_ptr [N+1] i32, *_nbr [E] i32, *_eid [E] i32; workspace: evi_graph_csr_workspace_bytes(N) = 8 * max(N, 1) bytes
+ *   (per-node counters for the graphs too large for LDS; 64 * max(N, 1) while an 8-part build existed). */
 size_t evi_graph_csr_workspace_bytes(int64_t N);
 int evi_graph_csr(const int64_t* edge_index, int64_t E, const int64_t* node_ptr, const int64_t* edge_ptr,
                   int B, int64_t N, int32_t* in_ptr, int32_t* in_nbr, int32_t* in_eid, int32_t* out_ptr,

@@ -475,18 +475,13 @@ def test_out_of_range_relation_id_on_the_hint_path_is_reported_not_read_out_of_b
     model.check_deferred()  # the flag was reset
 
 
-@pytest.mark.parametrize("parts", [0, 1, 2, 4, 8])
-def test_csr_parts_dde_and_bfs_agree_for_every_split(dev, parts, monkeypatch):
-    """The CSR is built from P edge-list parts per graph at small batches (B x P workgroups, LDS counters) and in one piece
-    at large ones: every P must give the same rows (as multisets; the order inside a row is unspecified), the same DDE
-    features and the same BFS levels.  The batch mixes tiny graphs, a hub, a graph without edges and one with more nodes
-    than the parts' LDS counters hold (built in one piece inside the scan kernel)."""
+def test_csr_dde_and_bfs_agree_with_the_oracle(dev, monkeypatch):
+    """The CSR build (one workgroup per (graph, side), rows staged in LDS and written out coalesced) must give the right rows
+    (as multisets; the order inside a row is unspecified), DDE features and BFS levels.  The batch mixes tiny graphs, a hub,
+    a graph without edges, and graphs beyond the build's LDS budget — the 20 000-edge and the 9 000-node ones, built by the
+    global-memory path inside the same kernel — and one exactly at it (8 192 nodes, 14 336 edges)."""
     from evi_rag_amd import _lib, ops
 
-    if parts:
-        monkeypatch.setenv("EVI_CSR_PARTS", str(parts))
-    else:  # the default build: one workgroup per (graph, side), rows staged in LDS and written out coalesced; the 20 000-edge
-        monkeypatch.delenv("EVI_CSR_PARTS", raising=False)  # and the 9 000-node graphs exceed its LDS budget (global build inside it)
     rng = np.random.default_rng(5)
     sizes = [(40, 90), (3000, 10000), (1, 0), (7000, 9000), (64, 4000), (500, 1), (300, 20000), (9000, 12000), (8192, 14336)]
     ei, ptr, eptr = [], [0], [0]

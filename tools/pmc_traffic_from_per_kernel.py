@@ -23,8 +23,8 @@ def main():
     a = ap.parse_args()
     N, D, Q, k = a.rows, a.dim, a.queries, a.k
     kk = k + max(256, k // 2)
-    legs = {"f32": ("_pmc_traffic.json", "k_cosine_score<2, 4, 1024, 0, 0>", "scan", N * D * 4 + Q * D * 4 + Q * k * 12, "--no-two-stage"),
-            "ts": ("_two_stage_pmc_traffic.json", "k_cosine_score<2, 4, 1024, 0, 1>", "two_stage", N * D * 2 + Q * D * 4 + Q * kk * 12,
+    legs = {"f32": ("_pmc_traffic.json", "k_cosine_score<2, 4, 0>", "scan", N * D * 4 + Q * D * 4 + Q * k * 12, "--no-two-stage"),
+            "ts": ("_two_stage_pmc_traffic.json", "k_cosine_score<2, 4, 1>", "two_stage", N * D * 2 + Q * D * 4 + Q * kk * 12,
                    "--topk-method two_stage --no-two-stage")}
     for leg, (suffix, kernel, method, alg, flags) in legs.items():
         src = os.path.join(a.dir, f"{a.tag}_pmc_{leg}_per_kernel.json")
@@ -53,7 +53,7 @@ def main():
                 continue
             d = v["dispatches"] / steps
             b = (v["fetch_bytes_per_dispatch"] + v["write_bytes_per_dispatch"]) * d
-            if method == "two_stage" and "k_cosine_score<2, 4, 1024, 0, 0>" in n:
+            if method == "two_stage" and "k_cosine_score<2, 4, 0>" in n:
                 continue  # the gated (closed) f32 launches of the device-side repair: no traffic to speak of
             others[n] = {"dispatches_per_step": d, "hbm_bytes_per_step": b}
             total += b
