@@ -60,6 +60,21 @@ class EviRetrieverOutput(Structure):
                 ("saved", c_void_p), ("saved_bytes", c_size_t)]
 
 
+EVI_OPTIM_MAX_GROUPS = 16
+EVI_OPTIM_RULES = {"adamw": 0, "adam": 1, "sgd": 2, "rmsprop": 3, "adagrad": 4, "adamax": 5, "nadam": 6, "adadelta": 7}
+EVI_OPTIM_OPT_AMSGRAD = 1
+EVI_OPTIM_OPT_NESTEROV = 2
+EVI_OPTIM_OPT_CENTERED = 2
+
+
+class EviOptimGroup(Structure):
+    """Mirror of `EviOptimGroup` in include/evi_hip.h."""
+
+    _fields_ = [("begin", c_int64), ("end", c_int64), ("step", c_int64), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)] + [
+        (name, ctypes.c_double) for name in ("lr", "weight_decay", "beta1", "beta2", "eps", "momentum", "dampening", "alpha",
+                                             "lr_decay", "momentum_decay", "mu_product")]
+
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "evi_version": (c_int, []),
@@ -131,6 +146,7 @@ _SIGNATURES = {
     "evi_grad_norm_workspace_bytes": (c_size_t, [c_int64]),
     "evi_grad_norm": (c_int, [_P, c_int64, c_float, _P, _P, c_size_t, _P]),
     "evi_adamw_step": (c_int, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int64, c_float, _P, c_float, _P]),
+    "evi_optim_step": (c_int, [c_int, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_float, _P, c_float, _P]),
     "evi_retriever_saved_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "evi_retriever_saved_bytes_full": (c_size_t, [c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int64, c_int]),
     "evi_retriever_backward": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P, c_size_t, _P]),

@@ -21,9 +21,12 @@ mixed modes with the reference's torch.autocast numerics is UNPINNED (no referen
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import time
-from typing import Any, Dict, Iterable, Mapping, Optional
+from collections import OrderedDict
+from fnmatch import fnmatch
+from typing import Any, Dict, Iterable, List, Mapping, Optional, Sequence
 
 import torch
 import torch.distributed as dist
@@ -104,29 +107,375 @@ class FlatAdamW:
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
 
 
-def setup_optimizer(module: torch.nn.Module, optimizer_cfg: Optional[Mapping[str, Any]]) -> FlatAdamW:
-    """`setup_optimizer` (src/utils/optimization.py:20-35) for the optimiser the retriever trains with (`type: adamw`)."""
+# ---- the reference's optimizer_cfg: rules, options, parameter groups ---------------------------------------------------------
+# rule -> (the options torch's constructor takes with their defaults, the names of the state buffers s0, s1, s2 of
+# evi_optim_step as torch's state_dict calls them).  `betas` / `rho` are torch's spellings; the C-ABI's fields are beta1 / beta2
+# and alpha.
+_RULES: Dict[str, Any] = {
+    "adamw": ({"lr": 1e-3, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 1e-2, "amsgrad": False},
+              ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")),
+    "adam": ({"lr": 1e-3, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0.0, "amsgrad": False},
+             ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")),
+    "sgd": ({"lr": 1e-3, "momentum": 0.0, "dampening": 0.0, "weight_decay": 0.0, "nesterov": False}, ("momentum_buffer", None, None)),
+    "rmsprop": ({"lr": 1e-2, "alpha": 0.99, "eps": 1e-8, "weight_decay": 0.0, "momentum": 0.0, "centered": False},
+                ("square_avg", "momentum_buffer", "grad_avg")),
+    "adagrad": ({"lr": 1e-2, "lr_decay": 0.0, "weight_decay": 0.0, "initial_accumulator_value": 0.0, "eps": 1e-10}, ("sum", None, None)),
+    "adamax": ({"lr": 2e-3, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0.0}, ("exp_avg", "exp_inf", None)),
+    "nadam": ({"lr": 2e-3, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0.0, "momentum_decay": 4e-3}, ("exp_avg", "exp_avg_sq", None)),
+    "adadelta": ({"lr": 1.0, "rho": 0.9, "eps": 1e-6, "weight_decay": 0.0}, ("square_avg", "acc_delta", None)),
+}
+# torch options that choose among torch's implementations of a rule, not the rule: accepted and ignored
+_IMPLEMENTATION_OPTIONS = ("foreach", "fused", "capturable", "differentiable")
+# torch options that change the rule and are not built: accepted only when off
+_UNBUILT_OPTIONS = ("maximize", "decoupled_weight_decay")
+_MUON_NAMES = ("muon", "singledevicemuon", "single_device_muon", "distributedmuon", "muon_distributed")
+MAX_PARAM_GROUPS = _lib.EVI_OPTIM_MAX_GROUPS
+
+
+def _plain(obj: Any) -> Any:
+    """An OmegaConf node as plain containers (the reference's configs arrive through Hydra); anything else as it is."""
+    try:
+        from omegaconf import DictConfig, ListConfig, OmegaConf
+    except Exception:
+        return obj
+    return OmegaConf.to_container(obj, resolve=True) if isinstance(obj, (DictConfig, ListConfig)) else obj
+
+
+def _name_matches(name: str, pattern: str) -> bool:
+    """One pattern of a group's `params` list (src/utils/optimization.py:158-170): a pattern with `*`, `?` or `[` is a glob
+    over the whole name; any other is the name itself, a module prefix (`pattern.`) or a suffix of the name."""
+    pattern = pattern.strip()
+    if not pattern:
+        return False
+    if "*" in pattern or "?" in pattern or "[" in pattern:
+        return fnmatch(name, pattern)
+    return name == pattern or name.startswith(pattern + ".") or name.endswith(pattern)
+
+
+def _group_configs(groups_cfg: Any) -> List[Mapping[str, Any]]:
+    """The three spellings of `param_groups` (optimization.py:134-151) as a list of group mappings: one group (a mapping
+    with `params` / `names`), a mapping of named groups, or a sequence of groups; entries that are no mappings are skipped."""
+    groups_cfg = _plain(groups_cfg)
+    if groups_cfg is None:
+        return []
+    if isinstance(groups_cfg, Mapping):
+        if "params" in groups_cfg or "names" in groups_cfg:
+            return [groups_cfg]
+        return [g for g in groups_cfg.values() if isinstance(g, Mapping)]
+    if isinstance(groups_cfg, Sequence) and not isinstance(groups_cfg, (str, bytes)):
+        return [g for g in groups_cfg if isinstance(g, Mapping)]
+    raise TypeError("param_groups must be a mapping or sequence of mappings.")
+
+
+def build_param_groups(module: torch.nn.Module, groups_cfg: Any):
+    """`_build_param_groups` (src/utils/optimization.py:82-131), device-free: the trainable parameters as a plain list (no
+    `param_groups`) or as torch-style group dicts `{"params": [...], **overrides}`.  Groups are taken in the order given and
+    a parameter belongs to the first group one of whose patterns matches its name; groups without patterns or without a
+    match are dropped; what no group claimed forms a last group without overrides (the optimiser's defaults)."""
+    named = OrderedDict((n, p) for n, p in module.named_parameters() if p.requires_grad)
+    if not named:
+        raise ValueError("Module has no trainable parameters.")
+    if not groups_cfg:
+        return list(named.values())
+    taken: set = set()
+    groups: List[Dict[str, Any]] = []
+    for cfg in _group_configs(groups_cfg):
+        cfg = dict(cfg or {})
+        patterns = cfg.pop("params", None) or cfg.pop("names", None)
+        if not patterns:
+            continue
+        if isinstance(patterns, str):
+            patterns = [patterns]
+        elif isinstance(patterns, Sequence):
+            patterns = list(patterns)
+        else:
+            raise TypeError("param group patterns must be a string or sequence of strings.")
+        members = [n for n in named if n not in taken and any(_name_matches(n, pat) for pat in patterns)]
+        if not members:
+            continue
+        taken.update(members)
+        group = {k: v for k, v in cfg.items() if k not in ("params", "names")}
+        group["params"] = [named[n] for n in members]
+        groups.append(group)
+    rest = [p for n, p in named.items() if n not in taken]
+    if rest:
+        groups.append({"params": rest})
+    if not groups:
+        raise ValueError("Param group configuration did not match any parameters.")
+    return groups
+
+
+def resolve_rule(name: str) -> str:
+    """The reference's optimiser names (optimization.py:46-79) -> a rule of evi_optim_step, or its refusal."""
+    name = str(name).lower()
+    if name in _RULES:
+        return name
+    if name == "lbfgs":
+        raise ValueError("Optimizer type 'lbfgs' is closure-based (it re-evaluates the loss inside a step) and is not supported by "
+                         "the flat optimiser.")
+    if name in _MUON_NAMES:
+        raise ImportError("Muon optimizer requested but the 'muon-optimizer' package is not installed. "
+                          "Install it via `pip install git+https://github.com/KellerJordan/Muon`.")
+    raise ValueError(f"Unsupported optimizer type '{name}' (this backend implements {', '.join(sorted(_RULES))}).")
+
+
+def _check_options(rule: str, options: Mapping[str, Any], where: str) -> Dict[str, Any]:
+    """Options of a rule as given in a config (defaults or one group's overrides), without the ones that only pick a torch
+    implementation.  An option the rule does not have is a TypeError, as from torch's constructor."""
+    known = _RULES[rule][0]
+    out = {}
+    for k, v in options.items():
+        if k in _IMPLEMENTATION_OPTIONS:
+            continue
+        if k in _UNBUILT_OPTIONS:
+            if v:
+                raise ValueError(f"{rule}: option '{k}' is not supported by the flat optimiser")
+            continue
+        if k not in known:
+            raise TypeError(f"{rule} ({where}) got an unexpected option '{k}' (it takes {', '.join(known)})")
+        out[k] = v
+    return out
+
+
+class FlatOptimizer:
+    """Any elementwise torch.optim rule with parameter groups over one flat buffer (csrc/optim.hip, evi_optim_step): what
+    the reference's `setup_optimizer` accepts beyond the default.  Same relation to the module as `FlatAdamW` — `params`
+    re-pointed into the buffer, `.grad`s as views of `self.grad` — but laid out group by group, so that a group is one range
+    and a step stays one gradient-norm pass plus one update launch.  `param_groups` is torch's list of dicts (`params`, `lr`,
+    `initial_lr`, the rule's options): schedulers and users read and set `lr` (or any option) per group between steps."""
+
+    def __init__(self, params, rule: str = "adamw", **defaults: Any) -> None:
+        rule = resolve_rule(rule)
+        self.rule = rule
+        base = dict(_RULES[rule][0])
+        base.update(_check_options(rule, defaults, "defaults"))
+        params = list(params)
+        if not params:
+            raise ValueError("optimizer got an empty parameter list")
+        raw_groups = params if isinstance(params[0], Mapping) else [{"params": params}]
+        self.param_groups: List[Dict[str, Any]] = []
+        seen: set = set()
+        for raw in raw_groups:
+            raw = dict(raw)
+            members = raw.pop("params")
+            members = [members] if isinstance(members, torch.Tensor) else list(members)
+            members = [p for p in members if p.requires_grad]
+            if any(id(p) in seen for p in members):
+                raise ValueError("some parameters appear in more than one parameter group")
+            seen.update(id(p) for p in members)
+            group = dict(base)
+            group.update(_check_options(rule, raw, "param group"))
+            group["lr"] = float(group["lr"])
+            group["initial_lr"] = group["lr"]
+            group["params"] = members
+            if members:
+                self.param_groups.append(group)
+        self.params = [p for g in self.param_groups for p in g["params"]]
+        if not self.params:
+            raise ValueError("optimizer got an empty parameter list")
+        if len(self.param_groups) > MAX_PARAM_GROUPS:
+            raise NotImplementedError(f"{len(self.param_groups)} parameter groups: the flat optimiser takes at most {MAX_PARAM_GROUPS} "
+                                      "(the group table travels in the kernel's arguments)")
+        dev = self.params[0].device
+        if dev.type != "cuda":
+            raise RuntimeError("FlatOptimizer runs on the MI355X only (there is no CPU fallback)")
+        if any(p.dtype != torch.float32 or p.device != dev for p in self.params):
+            raise ValueError("FlatOptimizer needs f32 parameters on one device")
+        # group by group; every parameter starts on a 16-byte boundary (the kernels use 16-byte accesses on the flat buffers)
+        offs, ranges, n = [], [], 0
+        for g in self.param_groups:
+            begin = n
+            for p in g["params"]:
+                offs.append(n)
+                n += (p.numel() + 3) // 4 * 4
+            ranges.append((begin, n))
+        self.numel, self._offsets, self._ranges = n, offs, ranges
+        self.flat = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.steps = [0] * len(self.param_groups)            # per group, as torch counts per parameter
+        self.mu_products = [1.0] * len(self.param_groups)    # nadam (one per group: the step count is shared within a group)
+        self._table = (_lib.EviOptimGroup * len(self.param_groups))()
+        self._fill_table()  # validates the hyper-parameters' types
+        # only the state buffers some group's options need
+        need = self._needed_state()
+        self.state: Dict[str, torch.Tensor] = {name: torch.zeros(n, dtype=torch.float32, device=dev)
+                                               for name, used in zip(_RULES[rule][1], need) if used}
+        if rule == "adagrad":
+            for g, (b, e) in zip(self.param_groups, ranges):
+                self.state["sum"][b:e].fill_(float(g["initial_accumulator_value"]))
+        with torch.no_grad():
+            for p, o in zip(self.params, offs):
+                view = self.flat[o:o + p.numel()].view_as(p)
+                view.copy_(p.data)
+                p.data = view
+                p.grad = self.grad[o:o + p.numel()].view_as(p)
+
+    # logging reads one rate: group 0's (Lightning's LearningRateMonitor names it `lr-<Optimizer>` the same way)
+    @property
+    def lr(self) -> float:
+        return self.param_groups[0]["lr"]
+
+    @property
+    def initial_lr(self) -> float:
+        return self.param_groups[0]["initial_lr"]
+
+    def _needed_state(self):
+        r, gs = self.rule, self.param_groups
+        if r in ("adamw", "adam"):
+            return True, True, any(bool(g["amsgrad"]) for g in gs)
+        if r == "sgd":
+            return any(float(g["momentum"]) != 0.0 for g in gs), False, False
+        if r == "rmsprop":
+            return True, any(float(g["momentum"]) > 0.0 for g in gs), any(bool(g["centered"]) for g in gs)
+        return True, _RULES[r][1][1] is not None, False
+
+    def _fill_table(self) -> None:
+        """param_groups (which schedulers and users may have changed) -> the C-ABI's group table, for the NEXT step."""
+        for i, (g, (b, e)) in enumerate(zip(self.param_groups, self._ranges)):
+            t = self._table[i]
+            t.begin, t.end, t.step = b, e, self.steps[i] + 1
+            t.lr, t.weight_decay, t.eps = float(g["lr"]), float(g["weight_decay"]), float(g.get("eps", 0.0))
+            b1, b2 = g.get("betas", (0.0, 0.0))
+            t.beta1, t.beta2 = float(b1), float(b2)
+            t.momentum, t.dampening = float(g.get("momentum", 0.0)), float(g.get("dampening", 0.0))
+            t.alpha = float(g["rho"] if self.rule == "adadelta" else g.get("alpha", 0.0))
+            t.lr_decay, t.momentum_decay = float(g.get("lr_decay", 0.0)), float(g.get("momentum_decay", 0.0))
+            t.mu_product = self.mu_products[i]
+            t.flags = ((_lib.EVI_OPTIM_OPT_AMSGRAD if g.get("amsgrad") else 0) | (_lib.EVI_OPTIM_OPT_NESTEROV if g.get("nesterov") else 0)
+                       | (_lib.EVI_OPTIM_OPT_CENTERED if g.get("centered") else 0))
+
+    def zero_grad(self) -> None:
+        self.grad.zero_()
+        for p, o in zip(self.params, self._offsets):  # a `.grad = None` by someone else would detach the views
+            if p.grad is None or p.grad.data_ptr() != self.grad.data_ptr() + 4 * o:
+                p.grad = self.grad[o:o + p.numel()].view_as(p)
+
+    def step(self, *, grad_scale: float = 1.0, max_norm: Optional[float] = None) -> None:
+        """One update of every group from `self.grad * grad_scale`, clipped to `max_norm` (total L2 norm over ALL groups)."""
+        lib = _lib.load()
+        dev = self.flat.device
+        s = ops._stream(dev)
+        need = self._needed_state()
+        if any(used and name not in self.state for name, used in zip(_RULES[self.rule][1], need)):
+            raise ValueError(f"{self.rule}: an option that needs another state buffer (amsgrad, momentum, centered) was switched on "
+                             "after construction")
+        self._fill_table()
+        norm_ptr = None
+        if max_norm is not None:
+            ws = ops._workspace(dev, "grad_norm", int(lib.evi_grad_norm_workspace_bytes(self.numel)))
+            _lib.check(lib.evi_grad_norm(self.grad.data_ptr(), self.numel, float(grad_scale), self.grad_norm.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), s))
+            norm_ptr = self.grad_norm.data_ptr()
+        bufs = [self.state[name].data_ptr() if name in self.state else None for name in _RULES[self.rule][1]]
+        _lib.check(lib.evi_optim_step(_lib.EVI_OPTIM_RULES[self.rule], self.flat.data_ptr(), self.grad.data_ptr(), bufs[0], bufs[1], bufs[2],
+                                      self.numel, ctypes.cast(self._table, ctypes.c_void_p), len(self.param_groups), float(grad_scale),
+                                      norm_ptr, float(max_norm or 0.0), s))
+        for i in range(len(self.steps)):
+            self.steps[i] += 1
+            self.mu_products[i] = float(self._table[i].mu_product)
+        # the kernel wrote the parameters behind torch's back: bump their version counters (no launch), as FlatAdamW does
+        torch.autograd.graph.increment_version(self.params)
+
+    def state_dict(self) -> Dict[str, Any]:
+        """Plain containers, scalars and tensors only (loadable with `torch.load(weights_only=True)`): the rule, per group the
+        options / step / mu_product / element range, and the flat state buffers under torch's names for them."""
+        groups = []
+        for g, st, mu, (b, e) in zip(self.param_groups, self.steps, self.mu_products, self._ranges):
+            d = {k: (list(v) if isinstance(v, (tuple, list)) else v) for k, v in g.items() if k != "params"}
+            d.update(step=st, mu_product=mu, begin=b, end=e)
+            groups.append(d)
+        return {"rule": self.rule, "numel": self.numel, "param_groups": groups, "state": {k: v.clone() for k, v in self.state.items()}}
+
+    def load_state_dict(self, sd: Mapping[str, Any]) -> None:
+        if "rule" not in sd:
+            raise ValueError("this optimiser state was written by FlatAdamW (the default configuration); load it into a trainer with "
+                             "the configuration that wrote it")
+        groups = list(sd["param_groups"])
+        if sd["rule"] != self.rule or int(sd["numel"]) != self.numel or len(groups) != len(self.param_groups) or \
+                any((int(d["begin"]), int(d["end"])) != r for d, r in zip(groups, self._ranges)) or set(sd["state"]) != set(self.state):
+            raise ValueError("optimiser state does not fit this optimiser (another rule, other parameter groups or options)")
+        for i, (g, d) in enumerate(zip(self.param_groups, groups)):
+            for k, v in d.items():
+                if k in ("step", "mu_product", "begin", "end"):
+                    continue
+                g[k] = tuple(v) if isinstance(v, (tuple, list)) else v
+            self.steps[i], self.mu_products[i] = int(d["step"]), float(d["mu_product"])
+        for k, v in sd["state"].items():
+            self.state[k].copy_(v)
+
+
+def setup_optimizer(module: torch.nn.Module, optimizer_cfg: Optional[Mapping[str, Any]]):
+    """`setup_optimizer` (src/utils/optimization.py:20-35): `type` / `name` picks the rule, `param_groups` the groups, every
+    other key is an option of the rule.  The retriever's default — adamw, one group, no amsgrad — is `FlatAdamW` (its own
+    kernel, layout and checkpoint keys); everything else is a `FlatOptimizer`."""
     if module is None:
         raise ValueError("setup_optimizer requires a valid nn.Module.")
-    cfg = dict(optimizer_cfg or {})
+    cfg = _plain(optimizer_cfg) or {}
+    if not isinstance(cfg, Mapping):
+        raise TypeError(f"optimizer_cfg must be a mapping, got {type(cfg)}.")
+    cfg = dict(cfg)
     opt_type = str(cfg.pop("type", cfg.pop("name", "adamw"))).lower()
-    if cfg.pop("param_groups", None):
-        raise NotImplementedError("param_groups are not supported by the flat optimiser (one group: all parameters)")
-    if opt_type != "adamw":
-        raise ValueError(f"Unsupported optimizer type '{opt_type}' (this backend implements the retriever's default, adamw).")
-    return FlatAdamW(module.parameters(), **cfg)
+    groups_cfg = cfg.pop("param_groups", None)
+    params = build_param_groups(module, groups_cfg)
+    rule = resolve_rule(opt_type)
+    if rule == "adamw" and not groups_cfg and not cfg.get("amsgrad"):
+        return FlatAdamW(params, **{k: v for k, v in _check_options(rule, cfg, "defaults").items() if k != "amsgrad"})
+    return FlatOptimizer(params, rule=rule, **cfg)
+
+
+def _each_rate(optimizer, rate) -> None:
+    """lr = rate(initial_lr) for every group of a FlatOptimizer, or for the one rate of a FlatAdamW."""
+    groups = getattr(optimizer, "param_groups", None)
+    if groups is None:
+        optimizer.lr = rate(optimizer.initial_lr)
+    else:
+        for g in groups:
+            g["lr"] = rate(g["initial_lr"])
 
 
 class CosineSchedule:
-    """torch.optim.lr_scheduler.CosineAnnealingLR in closed form, stepped per epoch (retriever_module.py:341-354)."""
+    """torch.optim.lr_scheduler.CosineAnnealingLR in closed form, stepped per epoch (retriever_module.py:341-354); every
+    group anneals from its own initial rate."""
 
-    def __init__(self, optimizer: FlatAdamW, t_max: int = 10, eta_min: float = 0.0) -> None:
+    def __init__(self, optimizer, t_max: int = 10, eta_min: float = 0.0) -> None:
         self.opt, self.t_max, self.eta_min, self.last_epoch = optimizer, int(t_max), float(eta_min), 0
 
     def step(self) -> None:
         self.last_epoch += 1
-        base = self.opt.initial_lr
-        self.opt.lr = self.eta_min + (base - self.eta_min) * (1.0 + math.cos(math.pi * self.last_epoch / self.t_max)) / 2.0
+        shape = (1.0 + math.cos(math.pi * self.last_epoch / self.t_max)) / 2.0
+        _each_rate(self.opt, lambda base: self.eta_min + (base - self.eta_min) * shape)
+
+
+class CosineRestartSchedule:
+    """torch.optim.lr_scheduler.CosineAnnealingWarmRestarts stepped per epoch (retriever_module.py:355-369: `cosine_restart`,
+    `cosine_warm_restarts`, `cosine_restarts`): lr = eta_min + (initial_lr - eta_min) (1 + cos(pi T_cur / T_i)) / 2, where
+    T_cur counts epochs since the last restart and the period T_i starts at t_0 and grows by t_mult at every restart.  The
+    position is a function of `last_epoch` alone, which is all a checkpoint keeps."""
+
+    def __init__(self, optimizer, t_0: int = 10, t_mult: int = 1, eta_min: float = 0.0) -> None:
+        if int(t_0) <= 0 or int(t_0) != t_0:
+            raise ValueError(f"Expected positive integer T_0, but got {t_0}")
+        if int(t_mult) < 1 or int(t_mult) != t_mult:
+            raise ValueError(f"Expected integer T_mult >= 1, but got {t_mult}")
+        self.opt, self.t_0, self.t_mult, self.eta_min, self.last_epoch = optimizer, int(t_0), int(t_mult), float(eta_min), 0
+
+    def position(self):
+        """(T_cur, T_i) at `last_epoch`."""
+        t_cur, t_i = self.last_epoch, self.t_0
+        while t_cur >= t_i:
+            t_cur -= t_i
+            t_i *= self.t_mult
+        return t_cur, t_i
+
+    def step(self) -> None:
+        self.last_epoch += 1
+        t_cur, t_i = self.position()
+        shape = (1.0 + math.cos(math.pi * t_cur / t_i)) / 2.0
+        _each_rate(self.opt, lambda base: self.eta_min + (base - self.eta_min) * shape)
+
+
+_RESTART_NAMES = ("cosine_restart", "cosine_warm_restarts", "cosine_restarts")
 
 
 def matmul_precision_for(precision: Any) -> str:
@@ -162,8 +511,11 @@ class RetrieverTrainer:
             self.scheduler = None
         elif stype == "cosine":
             self.scheduler = CosineSchedule(self.optimizer, t_max=int(sched.get("t_max", 10)), eta_min=float(sched.get("eta_min", 0.0)))
+        elif stype in _RESTART_NAMES:
+            self.scheduler = CosineRestartSchedule(self.optimizer, t_0=int(sched.get("t_0", 10)), t_mult=int(sched.get("t_mult", 1)),
+                                                   eta_min=float(sched.get("eta_min", 0.0)))
         else:
-            raise ValueError(f"Unsupported scheduler type '{stype}' (cosine or none).")
+            raise ValueError(f"Unsupported scheduler type '{stype}' (cosine, cosine_restart or none).")
         self.gradient_clip_val = None if not gradient_clip_val else float(gradient_clip_val)
         self.group = process_group
         self.global_step = 0
@@ -317,6 +669,17 @@ class RetrieverTrainer:
             self.scheduler.last_epoch = int(sd.get("scheduler_last_epoch", 0))
 
 
+def _on_host(obj: Any) -> Any:
+    """An optimiser state (FlatAdamW's flat mapping, FlatOptimizer's nested one) with its tensors on the host."""
+    if torch.is_tensor(obj):
+        return obj.detach().cpu()
+    if isinstance(obj, Mapping):
+        return {k: _on_host(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return [_on_host(v) for v in obj]
+    return obj
+
+
 def _save_checkpoint(self, path, callbacks: Optional[Mapping[str, Any]] = None) -> None:
     """A checkpoint in Lightning's layout as far as the reference reads it: `state_dict` with the retriever under the
     `model.` prefix of `RetrieverModule` (retriever_module.py:59) — what `src/eval.py:_load_checkpoint_strict` (:80-111) and
@@ -325,7 +688,7 @@ def _save_checkpoint(self, path, callbacks: Optional[Mapping[str, Any]] = None) 
     sd = self.state_dict()
     blob = {"state_dict": {f"model.{k}": v.detach().cpu() for k, v in sd["model"].items()}, "epoch": self.current_epoch,
             "global_step": self.global_step,
-            "optimizer_states": [{k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in sd["optimizer"].items()}],
+            "optimizer_states": [_on_host(sd["optimizer"])],
             "lr_schedulers": [{"last_epoch": sd["scheduler_last_epoch"]}]}
     if callbacks:
         # the run's selection state (Lightning keeps it under the same key): best score / path of model_checkpoint, best score /
@@ -346,4 +709,5 @@ def _load_checkpoint(self, path) -> Dict[str, Any]:
 RetrieverTrainer.save_checkpoint = _save_checkpoint
 RetrieverTrainer.load_checkpoint = _load_checkpoint
 
-__all__ = ["RetrieverTrainer", "FlatAdamW", "CosineSchedule", "setup_optimizer"]
+__all__ = ["RetrieverTrainer", "FlatAdamW", "FlatOptimizer", "CosineSchedule", "CosineRestartSchedule", "setup_optimizer",
+           "build_param_groups"]

@@ -693,6 +693,49 @@ int evi_grad_norm(const float* g, int64_t n, float scale, float* norm_out, void*
 int evi_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int64_t step, float grad_scale, const float* grad_norm, float max_norm, void* stream);
 
+/* evi_optim_step: the grouped, multi-rule form of the step — what the reference's setup_optimizer accepts beyond its default
+ * (src/utils/optimization.py:20-35, 82-170: any elementwise torch.optim rule, param_groups with per-group overrides).  One
+ * launch updates every group: a group is a contiguous range [begin, end) of the flat buffers on 16-byte boundaries (the host
+ * lays the parameters out group by group) with its own hyper-parameters and step count; at most EVI_OPTIM_MAX_GROUPS groups
+ * (the table travels by value in the kernel arguments; more -> EVI_ERR_UNSUPPORTED).  Every rule follows the order of
+ * operations of torch's single-tensor (foreach=False) implementation; step-dependent scalars are formed on the host in f64.
+ * grad_scale and the clip factor min(1, max_norm / (grad_norm[0] + 1e-6)) are shared by all groups; grad_norm NULL = no
+ * clipping.  State buffers (f32, n elements, zero-initialised unless noted; a buffer no group uses may be NULL):
+ *   rule      s0                                   s1                         s2                      fields read
+ *   ADAMW     exp_avg                              exp_avg_sq                 max_exp_avg_sq (AMSGRAD) beta1 beta2 eps
+ *   ADAM      (as ADAMW; weight_decay is the coupled L2 term g + wd p)
+ *   SGD       momentum_buffer (momentum != 0)      -                          -                       momentum dampening, NESTEROV
+ *   RMSPROP   square_avg                           momentum_buffer (momentum) grad_avg (CENTERED)     alpha eps momentum
+ *   ADAGRAD   sum (initial_accumulator_value)      -                          -                       lr_decay eps
+ *   ADAMAX    exp_avg                              exp_inf                    -                       beta1 beta2 eps
+ *   NADAM     exp_avg                              exp_avg_sq                 -                       beta1 beta2 eps momentum_decay mu_product
+ *   ADADELTA  square_avg                           acc_delta                  -                       alpha (= rho) eps
+ * lr and weight_decay are read by every rule.  NADAM: mu_product is the product of the momentum coefficients through the
+ * previous step (1 before the first); the call replaces it by the product through this step — host memory, no device work. */
+#define EVI_OPTIM_MAX_GROUPS 16
+#define EVI_OPTIM_ADAMW 0
+#define EVI_OPTIM_ADAM 1
+#define EVI_OPTIM_SGD 2
+#define EVI_OPTIM_RMSPROP 3
+#define EVI_OPTIM_ADAGRAD 4
+#define EVI_OPTIM_ADAMAX 5
+#define EVI_OPTIM_NADAM 6
+#define EVI_OPTIM_ADADELTA 7
+#define EVI_OPTIM_OPT_AMSGRAD 1  /* ADAMW, ADAM */
+#define EVI_OPTIM_OPT_MOMENTUM 1 /* set by the library from momentum (SGD, RMSPROP); ignored in flags */
+#define EVI_OPTIM_OPT_NESTEROV 2 /* SGD */
+#define EVI_OPTIM_OPT_CENTERED 2 /* RMSPROP */
+typedef struct EviOptimGroup {
+    int64_t begin, end; /* element range in the flat buffers; multiples of 4 */
+    int64_t step;       /* the count of THIS update, from 1 */
+    int32_t flags;      /* EVI_OPTIM_OPT_* of the rule */
+    int32_t reserved;
+    double lr, weight_decay, beta1, beta2, eps, momentum, dampening, alpha, lr_decay, momentum_decay;
+    double mu_product;  /* NADAM, in / out */
+} EviOptimGroup;
+int evi_optim_step(int rule, float* p, const float* g, float* s0, float* s1, float* s2, int64_t n, EviOptimGroup* groups,
+                   int num_groups, float grad_scale, const float* grad_norm, float max_norm, void* stream);
+
 /* ---- BFS candidate chains over g_agent samples (csrc/chains.hip) ---------------------------------------------------------
  * Replaces build_bfs_candidate_chains, src/data/components/bfs_chain_builder.py:49-311, for a flat batch of S samples that
  * share one set of settings.  Per sample s: nodes [node_ptr[s], node_ptr[s+1]) (node_entity i64), edges
