@@ -1,6 +1,7 @@
 // Shared host/device helpers for the evi_hip library (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -50,7 +51,7 @@ struct Bump {
 // ---- optional per-kernel timing (bench.py's roofline leg) -----------------------------------
 // When enabled, launch sites bracket their dominant kernel with hipEvents on the call's stream;
 // evi_timing_read() synchronises those events and returns the summed durations per class.
-enum TimingClass { kTimeCosineScore = 0, kTimeSelect = 1, kTimeGemm = 2, kTimeEdge = 3, kTimeClasses = 8 };
+enum TimingClass { kUntimed = -1, kTimeCosineScore = 0, kTimeSelect = 1, kTimeGemm = 2, kTimeEdge = 3, kTimeClasses = 8 };
 bool timing_enabled();
 // Records a start event on `st`; returns a token (or -1 when timing is off).
 int timing_begin(int cls, hipStream_t st);
@@ -60,6 +61,16 @@ void timing_end(int token, hipStream_t st);
 // stream (each recorded event costs ~5 us of gap, ~60 us per scan step), so a timed run runs like an untimed one.
 // Returns false (and null events) when timing is off.
 bool timing_kernel_events(int cls, hipEvent_t* start, hipEvent_t* stop);
+// Launches `kernel` as ONE timed span of class `cls` when timing is on, as a plain launch otherwise; cls == kUntimed
+// keeps the launch out of the accounts.
+template <class... Params, class... Args>
+inline void launch_timed(int cls, void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    hipEvent_t start, stop;
+    if (cls != kUntimed && timing_kernel_events(cls, &start, &stop))
+        hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, st, start, stop, 0, static_cast<Params>(args)...);
+    else
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<Params>(args)...);
+}
 
 // ---- shared launchers ------------------------------------------------------------------------
 // C[M,N] = act(A[M,K] W[N,K]^T + bias); act: 0 none, 1 tanh, 2 sigmoid (gemm.hip).

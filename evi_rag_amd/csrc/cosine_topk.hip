@@ -24,7 +24,6 @@
 // Bound: HBM.  Algorithmic bytes per batch = N*D*4 + N*4 (row_scale, optional) + Q*D*4 + Q*k*12.
 #include "common.hpp"
 
-#include <hip/hip_ext.h>
 #include <hip/hip_fp8.h>
 
 #include <stdlib.h>
@@ -38,6 +37,21 @@ constexpr int64_t kFirstSegment = 65536;      // dense segment: every score is w
 constexpr int kCntStride = 64;                // one append cursor per 256 B: no false sharing between queries
 constexpr int64_t kSegmentGrowth = 16;
 constexpr int64_t kMaxSegmentDefault = 1 << 24;  // recommended workspace: 8 B x 32 x (min(N, 2^24) + k)
+
+// How the index is stored and multiplied; the values are k_cosine_score's third template argument.
+enum IndexKind : int {
+    kIdxF32 = 0,       // f32 rows, exact f32 MFMA chain
+    kIdxF16 = 1,       // f16 rows, query split hi + lo in f16
+    kIdxFp8Widen = 2,  // e4m3 rows + row_scale, bytes widened to f16 in registers
+    kIdxFp8Mfma = 3,   // e4m3 rows + row_scale on the native fp8 MFMA, query as two e4m3 pieces
+};
+static int index_chunks(IndexKind kind, int D) {  // 64-byte pieces of a row
+    return kind >= kIdxFp8Widen ? D / 64 : (kind == kIdxF16 ? D / 32 : D / 16);
+}
+// bytes of nq queries' fragments: two 1-byte pieces per element for the native fp8 MFMA, 4 bytes per element otherwise
+static size_t query_frag_bytes(IndexKind kind, int D, int nq) {
+    return kind == kIdxFp8Mfma ? (size_t)D * 2 * nq : (size_t)D * nq * sizeof(float);
+}
 
 // Device-side gate: a scan enqueued as the FALLBACK of a proof-carrying fast path (two-stage scan) takes a pointer to that
 // path's per-call status word; while the word is 0 (proof held) every kernel of the fallback returns at once, so the
@@ -126,7 +140,7 @@ __global__ void k_query_fragments_fp8(const float* __restrict__ q, int Q, int D,
     }
 }
 
-// NATIVE fp8 MFMA variant (F16 == 3): the e4m3 index bytes feed v_mfma_f32_16x16x32_fp8_fp8 as they are, so the query
+// NATIVE fp8 MFMA variant (kIdxFp8Mfma): the e4m3 index bytes feed v_mfma_f32_16x16x32_fp8_fp8 as they are, so the query
 // has to be fp8 too.  It is written as TWO e4m3 pieces with a power-of-two scale each,
 //     q ~ s1 * p1 + s2 * p2,   p1 = e4m3(q / s1),  p2 = e4m3((q - s1 p1) / s2),
 // (8 significant bits: |q - s1 p1 - s2 p2| <= 2^-8 |q|_inf per element, ~20x below the index's own e4m3 rounding), one
@@ -429,6 +443,17 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
     }
 }
 
+// The k output slots of query qi from sh.keys[0..m): (score, row_id_base + id), then (-inf, -1).  A key 0 inside [0, m)
+// is padding too; no real entry encodes to 0 (row ids are < 2^31 - 1, so the low word 0xFFFFFFFF - id is never 0).
+__device__ inline void write_topk(const SelectShared& sh, int m, int qi, int k, int64_t row_id_base,
+                                  float* __restrict__ out_score, int64_t* __restrict__ out_index) {
+    for (int i = threadIdx.x; i < k; i += blockDim.x) {
+        const uint64_t key = i < m ? sh.keys[i] : 0ull;
+        out_score[(int64_t)qi * k + i] = key != 0ull ? key_score(key) : -INFINITY;
+        out_index[(int64_t)qi * k + i] = key != 0ull ? row_id_base + (int64_t)key_index(key) : -1;
+    }
+}
+
 // One workgroup per query: exact top-k of its candidate list, written back sorted to the head of
 // the list; raises tau to the k-th score.  The last call of a batch also writes the outputs.
 __global__ __launch_bounds__(kSelectThreads) void k_candidates_select(
@@ -458,18 +483,7 @@ __global__ __launch_bounds__(kSelectThreads) void k_candidates_select(
         cand_cnt[qi * kCntStride] = m;
         if (m == k) tau[qi] = key_score(sh.keys[k - 1]);
     }
-    if (final_pass) {
-        for (int i = threadIdx.x; i < k; i += blockDim.x) {
-            if (i < m) {
-                const uint64_t key = sh.keys[i];
-                out_score[(int64_t)qi * k + i] = key_score(key);
-                out_index[(int64_t)qi * k + i] = row_id_base + (int64_t)key_index(key);
-            } else {
-                out_score[(int64_t)qi * k + i] = -INFINITY;
-                out_index[(int64_t)qi * k + i] = -1;
-            }
-        }
-    }
+    if (final_pass) write_topk(sh, m, qi, k, row_id_base, out_score, out_index);
 }
 
 struct WsLayout {
@@ -479,19 +493,14 @@ struct WsLayout {
 
 static WsLayout ws_layout(int D, int k, int64_t seg_max) {
     WsLayout w;
-    size_t off = 0;
-    w.qfrag_off = off;
-    off = align_up(off + (size_t)D * kQueryBlock * sizeof(float), 256);
-    w.tau_off = off;
-    off = align_up(off + kQueryBlock * sizeof(float), 256);
-    w.cnt_off = off;
-    off = align_up(off + (size_t)kQueryBlock * kCntStride * sizeof(int32_t), 256);
+    Bump m;
     w.cap = seg_max + k;
-    w.score_off = off;
-    off = align_up(off + (size_t)kQueryBlock * w.cap * sizeof(float), 256);
-    w.id_off = off;
-    off = align_up(off + (size_t)kQueryBlock * w.cap * sizeof(int32_t), 256);
-    w.total = off;
+    w.qfrag_off = m.take((size_t)D * kQueryBlock * sizeof(float));
+    w.tau_off = m.take(kQueryBlock * sizeof(float));
+    w.cnt_off = m.take((size_t)kQueryBlock * kCntStride * sizeof(int32_t));
+    w.score_off = m.take((size_t)kQueryBlock * w.cap * sizeof(float));
+    w.id_off = m.take((size_t)kQueryBlock * w.cap * sizeof(int32_t));
+    w.total = m.total;
     return w;
 }
 
@@ -516,35 +525,62 @@ struct ScoreArgs {
     int64_t cap;
     int dense, capq;
     const int32_t* gate;
-    hipEvent_t ev_start, ev_stop;  // non-null: stamped with the dispatch's begin / end (bench roofline leg)
 };
 
-template <int NQB, int U, int F16>
+template <int NQB, int U, int KIND>
 static int launch_score(const ScoreArgs& a) {
     static thread_local bool attr_set = false;
     if (!attr_set) {
-        EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cosine_score<NQB, U, F16>),
+        EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cosine_score<NQB, U, KIND>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
-    if (a.ev_start)
-        hipExtLaunchKernelGGL((k_cosine_score<NQB, U, F16>), dim3(a.grid), dim3(kScanThreads), (uint32_t)a.lds, a.st,
-                              a.ev_start, a.ev_stop, 0, a.qfrag, a.idx, a.b, a.e, a.D, a.Q, a.row_scale, a.tau, a.cs, a.ci,
-                              a.cc, a.cap, a.dense, a.capq, a.gate);
-    else
-        hipLaunchKernelGGL((k_cosine_score<NQB, U, F16>), dim3(a.grid), dim3(kScanThreads), a.lds, a.st,
-                           a.qfrag, a.idx, a.b, a.e, a.D, a.Q, a.row_scale, a.tau, a.cs, a.ci, a.cc, a.cap,
-                           a.dense, a.capq, a.gate);
+    // gated launches (the fallback of a proof-carrying path) stay out of the timing accounts
+    launch_timed(a.gate ? kUntimed : kTimeCosineScore, k_cosine_score<NQB, U, KIND>, dim3(a.grid), dim3(kScanThreads), a.lds,
+                 a.st, a.qfrag, a.idx, a.b, a.e, a.D, a.Q, a.row_scale, a.tau, a.cs, a.ci, a.cc, a.cap, a.dense, a.capq, a.gate);
     EVI_LAUNCH_CHECK();
     return EVI_OK;
 }
 
-template <int NQB, int F16>
+template <int NQB, int KIND>
 static int launch_score_u(int U, const ScoreArgs& a) {
     switch (U) {
-        case 4: return launch_score<NQB, 4, F16>(a);
-        case 2: return launch_score<NQB, 2, F16>(a);
-        default: return launch_score<NQB, 1, F16>(a);
+        case 4: return launch_score<NQB, 4, KIND>(a);
+        case 2: return launch_score<NQB, 2, KIND>(a);
+        default: return launch_score<NQB, 1, KIND>(a);
+    }
+}
+
+static int launch_score_kind(IndexKind kind, int nqb, int U, const ScoreArgs& a) {
+    switch (kind * 2 + (nqb - 1)) {
+        case kIdxF32 * 2: return launch_score_u<1, kIdxF32>(U, a);
+        case kIdxF32 * 2 + 1: return launch_score_u<2, kIdxF32>(U, a);
+        case kIdxF16 * 2: return launch_score_u<1, kIdxF16>(U, a);
+        case kIdxF16 * 2 + 1: return launch_score_u<2, kIdxF16>(U, a);
+        case kIdxFp8Widen * 2: return launch_score_u<1, kIdxFp8Widen>(U, a);
+        case kIdxFp8Widen * 2 + 1: return launch_score_u<2, kIdxFp8Widen>(U, a);
+        case kIdxFp8Mfma * 2: return launch_score_u<1, kIdxFp8Mfma>(U, a);
+        default: return launch_score_u<2, kIdxFp8Mfma>(U, a);
+    }
+}
+
+// the batch's query fragments in the layout `kind` multiplies (also resets the batch's selection state)
+static void launch_query_fragments(IndexKind kind, hipStream_t st, const float* q, int Q, int D, int nq_pad, float* qfrag,
+                                   float* tau, int32_t* cnt, const int32_t* gate) {
+    f16x8* qfrag16 = reinterpret_cast<f16x8*>(qfrag);
+    switch (kind) {
+        case kIdxFp8Mfma:  // one workgroup per query slot
+            hipLaunchKernelGGL(k_query_fragments_fp8n, dim3(nq_pad), dim3(256), 0, st, q, Q, D, nq_pad,
+                               reinterpret_cast<uint64_t*>(qfrag), tau, cnt, gate);
+            break;
+        case kIdxFp8Widen:
+            hipLaunchKernelGGL(k_query_fragments_fp8, dim3(32), dim3(256), 0, st, q, Q, D, nq_pad, qfrag16, tau, cnt, gate);
+            break;
+        case kIdxF16:
+            hipLaunchKernelGGL(k_query_fragments_f16, dim3(32), dim3(256), 0, st, q, Q, D, nq_pad, qfrag16, tau, cnt, gate);
+            break;
+        default:
+            hipLaunchKernelGGL(k_query_fragments, dim3(32), dim3(256), 0, st, q, Q, D, nq_pad, qfrag, tau, cnt, gate);
     }
 }
 
@@ -596,7 +632,7 @@ extern "C" size_t evi_cosine_topk_min_workspace_bytes(int Q, int64_t N, int D, i
     return ws_layout(D, k, clamp_seg(N, kFirstSegment)).total;
 }
 
-static int cosine_topk_impl(const float* q, int Q, const void* idx, int f16, int64_t N, int D,
+static int cosine_topk_impl(const float* q, int Q, const void* idx, IndexKind kind, int64_t N, int D,
                             const float* row_scale, int k, int64_t row_id_base, float* out_score,
                             int64_t* out_index, void* workspace, size_t workspace_bytes, void* stream,
                             const int32_t* gate = nullptr) {
@@ -611,11 +647,11 @@ static int cosine_topk_impl(const float* q, int Q, const void* idx, int f16, int
     if (D < 16 || D % 16 != 0 || D > 1280)
         return fail(EVI_ERR_UNSUPPORTED,
                     "evi_cosine_topk: D must be a multiple of 16 in [16, 1280], got %d", D);
-    if (f16 == 1 && D % 32 != 0)
+    if (kind == kIdxF16 && D % 32 != 0)
         return fail(EVI_ERR_UNSUPPORTED, "evi_cosine_topk_f16: D must be a multiple of 32, got %d", D);
-    if (f16 >= 2 && D % 64 != 0)
+    if (kind >= kIdxFp8Widen && D % 64 != 0)
         return fail(EVI_ERR_UNSUPPORTED, "evi_cosine_topk_fp8: D must be a multiple of 64, got %d", D);
-    EVI_REQUIRE(f16 < 2 || row_scale || N == 0, "evi_cosine_topk_fp8: row_scale (the per-row dequantisation scale) is required");
+    EVI_REQUIRE(kind < kIdxFp8Widen || row_scale || N == 0, "evi_cosine_topk_fp8: row_scale (the per-row dequantisation scale) is required");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
     const size_t min_ws = evi_cosine_topk_min_workspace_bytes(Q, N, D, k);
@@ -635,7 +671,7 @@ static int cosine_topk_impl(const float* q, int Q, const void* idx, int f16, int
     float* cs = reinterpret_cast<float*>(base + w.score_off);
     int32_t* ci = reinterpret_cast<int32_t*>(base + w.id_off);
 
-    const int chunks = f16 >= 2 ? D / 64 : (f16 ? D / 32 : D / 16);
+    const int chunks = index_chunks(kind, D);
     // loads in flight per lane per group: the largest U <= kScanMaxU that leaves an EVEN number of groups
     // (copy-free ping-pong), else the largest U that divides the row.
     int U = 1;
@@ -649,8 +685,7 @@ static int cosine_topk_impl(const float* q, int Q, const void* idx, int f16, int
 
     // 32 queries per pass when their fragments (+ the append counters) fit the 160 KiB of LDS, else 16: at D = 1280 the
     // f32 / f16 / widened-fp8 fragments of 32 queries are exactly 160 KiB and leave no room for the counters
-    const size_t frag_bytes_32 = f16 == 3 ? (size_t)D * 2 * kQueryBlock : (size_t)D * kQueryBlock * sizeof(float);
-    const int qblock = frag_bytes_32 + kQueryBlock * sizeof(int) > 160 * 1024 ? 16 : kQueryBlock;
+    const int qblock = query_frag_bytes(kind, D, kQueryBlock) + kQueryBlock * sizeof(int) > 160 * 1024 ? 16 : kQueryBlock;
     for (int q0 = 0; q0 < Q; q0 += qblock) {
         const int qn = (Q - q0) < qblock ? (Q - q0) : qblock;
         const int nqb = qn <= 16 ? 1 : 2;
@@ -658,18 +693,7 @@ static int cosine_topk_impl(const float* q, int Q, const void* idx, int f16, int
         float* o_score = out_score + (int64_t)q0 * k;
         int64_t* o_index = out_index + (int64_t)q0 * k;
 
-        if (f16 == 3)
-            hipLaunchKernelGGL(k_query_fragments_fp8n, dim3(nq_pad), dim3(256), 0, st, q + (int64_t)q0 * D, qn, D, nq_pad,
-                               reinterpret_cast<uint64_t*>(qfrag), tau, cnt, gate);
-        else if (f16 == 2)
-            hipLaunchKernelGGL(k_query_fragments_fp8, dim3(32), dim3(256), 0, st, q + (int64_t)q0 * D, qn, D, nq_pad,
-                               reinterpret_cast<f16x8*>(qfrag), tau, cnt, gate);
-        else if (f16)
-            hipLaunchKernelGGL(k_query_fragments_f16, dim3(32), dim3(256), 0, st, q + (int64_t)q0 * D, qn, D, nq_pad,
-                               reinterpret_cast<f16x8*>(qfrag), tau, cnt, gate);
-        else
-            hipLaunchKernelGGL(k_query_fragments, dim3(32), dim3(256), 0, st, q + (int64_t)q0 * D, qn, D,
-                               nq_pad, qfrag, tau, cnt, gate);
+        launch_query_fragments(kind, st, q + (int64_t)q0 * D, qn, D, nq_pad, qfrag, tau, cnt, gate);
         EVI_LAUNCH_CHECK();
 
         if (N == 0) {
@@ -678,7 +702,7 @@ static int cosine_topk_impl(const float* q, int Q, const void* idx, int f16, int
             EVI_LAUNCH_CHECK();
             continue;
         }
-        const size_t lds_q_bytes = f16 == 3 ? (size_t)D * 2 * nq_pad : (size_t)(D / 16) * 4 * nq_pad * sizeof(float4);
+        const size_t lds_q_bytes = query_frag_bytes(kind, D, nq_pad);
         // staging entries per query: whatever LDS is left, at most 64
         const int64_t lds_left = (int64_t)160 * 1024 - (int64_t)lds_q_bytes - (int64_t)(kQueryBlock * sizeof(int));
         int capq = lds_left > 0 ? (int)(lds_left / (kQueryBlock * 8)) : 0;
@@ -694,24 +718,13 @@ static int cosine_topk_impl(const float* q, int Q, const void* idx, int f16, int
             const int64_t tiles = (end - begin + 15) / 16;
             int64_t want = (tiles + waves_per_block - 1) / waves_per_block;
             const int grid = (int)(want < cus ? want : cus);
-            ScoreArgs sa{grid, lds, st, qfrag, idx, begin, end, D, qn, row_scale, tau,
-                         cs, ci, cnt, w.cap, first ? 1 : 0, capq, gate, nullptr, nullptr};
-            if (!gate) timing_kernel_events(kTimeCosineScore, &sa.ev_start, &sa.ev_stop);  // gated launches stay out of the accounts
-            const int rc = f16 == 3 ? (nqb == 1 ? launch_score_u<1, 3>(U, sa) : launch_score_u<2, 3>(U, sa))
-                           : f16 == 2 ? (nqb == 1 ? launch_score_u<1, 2>(U, sa) : launch_score_u<2, 2>(U, sa))
-                           : f16  ? (nqb == 1 ? launch_score_u<1, 1>(U, sa) : launch_score_u<2, 1>(U, sa))
-                                  : (nqb == 1 ? launch_score_u<1, 0>(U, sa) : launch_score_u<2, 0>(U, sa));
+            const ScoreArgs sa{grid, lds, st, qfrag, idx, begin, end, D, qn, row_scale, tau,
+                               cs, ci, cnt, w.cap, first ? 1 : 0, capq, gate};
+            const int rc = launch_score_kind(kind, nqb, U, sa);
             if (rc != EVI_OK) return rc;
             const int final_pass = end >= N ? 1 : 0;
-            hipEvent_t sel_start, sel_stop;
-            if (!gate && timing_kernel_events(kTimeSelect, &sel_start, &sel_stop))
-                hipExtLaunchKernelGGL(k_candidates_select, dim3(qn), dim3(kSelectThreads), 0, st, sel_start, sel_stop, 0, cs, ci,
-                                      cnt, tau, w.cap, k, first ? (end - begin) : (int64_t)-1, final_pass, row_id_base, o_score,
-                                      o_index, gate);
-            else
-                hipLaunchKernelGGL(k_candidates_select, dim3(qn), dim3(kSelectThreads), 0, st, cs, ci, cnt,
-                                   tau, w.cap, k, first ? (end - begin) : (int64_t)-1, final_pass,
-                                   row_id_base, o_score, o_index, gate);
+            launch_timed(gate ? kUntimed : kTimeSelect, k_candidates_select, dim3(qn), dim3(kSelectThreads), 0, st, cs, ci, cnt,
+                         tau, w.cap, k, first ? (end - begin) : (int64_t)-1, final_pass, row_id_base, o_score, o_index, gate);
             EVI_LAUNCH_CHECK();
             begin = end;
             first = false;
@@ -727,7 +740,7 @@ extern "C" int evi_cosine_topk(const float* q, int Q, const float* idx, int64_t 
                                const float* row_scale, int k, int64_t row_id_base, float* out_score,
                                int64_t* out_index, void* workspace, size_t workspace_bytes,
                                void* stream) {
-    return cosine_topk_impl(q, Q, idx, 0, N, D, row_scale, k, row_id_base, out_score, out_index, workspace,
+    return cosine_topk_impl(q, Q, idx, kIdxF32, N, D, row_scale, k, row_id_base, out_score, out_index, workspace,
                             workspace_bytes, stream);
 }
 
@@ -735,7 +748,7 @@ extern "C" int evi_cosine_topk_f16(const float* q, int Q, const void* idx_f16, i
                                    const float* row_scale, int k, int64_t row_id_base, float* out_score,
                                    int64_t* out_index, void* workspace, size_t workspace_bytes,
                                    void* stream) {
-    return cosine_topk_impl(q, Q, idx_f16, 1, N, D, row_scale, k, row_id_base, out_score, out_index, workspace,
+    return cosine_topk_impl(q, Q, idx_f16, kIdxF16, N, D, row_scale, k, row_id_base, out_score, out_index, workspace,
                             workspace_bytes, stream);
 }
 
@@ -743,14 +756,14 @@ extern "C" int evi_cosine_topk_fp8(const float* q, int Q, const void* idx_fp8, i
                                    const float* row_scale, int k, int64_t row_id_base, float* out_score,
                                    int64_t* out_index, void* workspace, size_t workspace_bytes,
                                    void* stream) {
-    return cosine_topk_impl(q, Q, idx_fp8, 2, N, D, row_scale, k, row_id_base, out_score, out_index, workspace,
+    return cosine_topk_impl(q, Q, idx_fp8, kIdxFp8Widen, N, D, row_scale, k, row_id_base, out_score, out_index, workspace,
                             workspace_bytes, stream);
 }
 
 extern "C" int evi_cosine_topk_fp8_mfma(const float* q, int Q, const void* idx_fp8, int64_t N, int D,
                                         const float* row_scale, int k, int64_t row_id_base, float* out_score,
                                         int64_t* out_index, void* workspace, size_t workspace_bytes, void* stream) {
-    return cosine_topk_impl(q, Q, idx_fp8, 3, N, D, row_scale, k, row_id_base, out_score, out_index, workspace,
+    return cosine_topk_impl(q, Q, idx_fp8, kIdxFp8Mfma, N, D, row_scale, k, row_id_base, out_score, out_index, workspace,
                             workspace_bytes, stream);
 }
 
@@ -826,21 +839,28 @@ __global__ void k_gt_clamp(int32_t* cnt, int Q) {
     if (i < Q && cnt[i * kCntStride] > kGemmTopkCap) cnt[i * kCntStride] = kGemmTopkCap;
 }
 
-// gap test: with kk rows kept, the true top-k is among them iff approx[k-1] - approx[kk-1] > 2 eps |q|
+// The proof both fast paths share: with kk rows kept by approximate score, the true top-k is among them when
+// approx[k-1] - approx[kk-1] > 2 eps |q|.  wave_sumsq is |q|^2 in ONE fixed order (lane-strided fmaf, xor butterfly), to
+// all 64 lanes; which lists are tested and which flags a failure raises is the caller's policy.
+__device__ inline float wave_sumsq(const float* __restrict__ q, int D, int lane) {
+    float ss = 0.f;
+    for (int d = lane; d < D; d += 64) ss = fmaf(q[d], q[d], ss);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+    return ss;
+}
+__device__ inline bool gap_fails(float gap, float eps, float ss) { return !(gap > 2.0f * eps * sqrtf(ss)); }  // NaN fails too
+
 __global__ void k_gt_gap(const float* __restrict__ q, int Q, int D, const float* __restrict__ cand_score,
                          const int32_t* __restrict__ cand_cnt, int k, int kk, float eps, int32_t* __restrict__ status) {
     const int qi = blockIdx.x;
     const int lane = threadIdx.x;  // one wave
-    float ss = 0.f;
-    for (int d = lane; d < D; d += 64) ss = fmaf(q[(int64_t)qi * D + d], q[(int64_t)qi * D + d], ss);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+    const float ss = wave_sumsq(q + (int64_t)qi * D, D, lane);
     if (lane == 0) {
         const int m = cand_cnt[qi * kCntStride];
         if (m >= kk) {
             const float* s = cand_score + (int64_t)qi * kGemmTopkCap;
-            const float gap = s[k - 1] - s[kk - 1];
-            if (!(gap > 2.0f * eps * sqrtf(ss))) atomicOr(status, 1);
+            if (gap_fails(s[k - 1] - s[kk - 1], eps, ss)) atomicOr(status, 1);
         }  // m < kk: every row of the index is in the list
     }
 }
@@ -848,23 +868,12 @@ __global__ void k_gt_gap(const float* __restrict__ q, int Q, int D, const float*
 // Exact re-scoring of candidate rows with the scan's arithmetic: the score of (query, row) is the chain
 //   for j = 0 .. D/16 - 1, e = 0 .. 3:  acc = mfma_16x16x4(a = q[16 j + 4 g + e], b = x[16 j + 4 g + e], acc)
 // over lane groups g = 0..3 — exactly what k_cosine_score feeds for that pair (an MFMA output element depends
-// only on its own row of A and column of B), times row_scale.  One wave per (query, 16 candidates): the query
-// sits in row 0 of A, the candidates in the 16 columns of B.
-__global__ __launch_bounds__(256) void k_gt_rescore(const float* __restrict__ q, int D, const float* __restrict__ idx,
-                                                    const float* __restrict__ row_scale, const int32_t* __restrict__ cand_id,
-                                                    const int32_t* __restrict__ cand_cnt, int Q, int kk,
-                                                    float* __restrict__ exact /* [Q, kk] */) {
-    const int lane = threadIdx.x & 63;
-    const int n = lane & 15, g = lane >> 4;
-    const int tiles = (kk + 15) / 16;
-    const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (w >= (int64_t)Q * tiles) return;  // whole waves only: the MFMAs below run with all 64 lanes
-    const int qi = (int)(w / tiles), t = (int)(w % tiles);
-    const int m = cand_cnt[qi * kCntStride] < kk ? cand_cnt[qi * kCntStride] : kk;
-    const int c = t * 16 + n;
-    const int32_t row = c < m ? cand_id[(int64_t)qi * kGemmTopkCap + c] : -1;
-    const f32x4* xp = reinterpret_cast<const f32x4*>(idx + (int64_t)(row >= 0 ? row : 0) * D) + g;
-    const f32x4* qp = reinterpret_cast<const f32x4*>(q + (int64_t)qi * D) + g;
+// only on its own row of A and column of B).  One wave per (query, 16 candidates): the query sits in row 0 of A, the
+// candidates (lane n = l & 15 brings row x) in the 16 columns of B; D[row 0][col n] is returned to the lanes with g == 0.
+// This chain IS the bit-exactness contract of the GEMM-shaped and two-stage paths with the scan.
+__device__ inline float rescore_chain(const float* __restrict__ q, const float* __restrict__ x_row, int D, int n, int g) {
+    const f32x4* xp = reinterpret_cast<const f32x4*>(x_row) + g;
+    const f32x4* qp = reinterpret_cast<const f32x4*>(q) + g;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     // eight 64-byte pieces of the row in flight per lane group: the rows are scattered over the index, so a loop that
@@ -886,39 +895,21 @@ __global__ __launch_bounds__(256) void k_gt_rescore(const float* __restrict__ q,
                 for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][e], x[u][e], acc, 0, 0, 0);
             }
     }
-    // D[row 0][col n] is register 0 of the lanes with g == 0
-    if (g == 0 && c < kk) {
-        float s = -INFINITY;
-        if (row >= 0) s = row_scale ? acc[0] * row_scale[row] : acc[0];
-        exact[(int64_t)qi * kk + c] = s;
-    }
+    return acc[0];
 }
 
 // The same for an f16-stored index: the scan multiplies the f16 rows with the query split hi + lo (lo scaled by
 // kLoScale) on v_mfma_f32_16x16x32_f16 into two accumulators, chunk by chunk of 32 dims, and combines them as
-// fma(acc_lo, 1 / kLoScale, acc).  Replayed here for (query in row 0, 16 candidates in the columns).
-__global__ __launch_bounds__(256) void k_gt_rescore_f16(const float* __restrict__ q, int D, const _Float16* __restrict__ idx,
-                                                        const float* __restrict__ row_scale, const int32_t* __restrict__ cand_id,
-                                                        const int32_t* __restrict__ cand_cnt, int Q, int kk,
-                                                        float* __restrict__ exact) {
-    const int lane = threadIdx.x & 63;
-    const int n = lane & 15, g = lane >> 4;
-    const int tiles = (kk + 15) / 16;
-    const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (w >= (int64_t)Q * tiles) return;
-    const int qi = (int)(w / tiles), t = (int)(w % tiles);
-    const int m = cand_cnt[qi * kCntStride] < kk ? cand_cnt[qi * kCntStride] : kk;
-    const int c = t * 16 + n;
-    const int32_t row = c < m ? cand_id[(int64_t)qi * kGemmTopkCap + c] : -1;
-    const f16x8* xp = reinterpret_cast<const f16x8*>(idx + (int64_t)(row >= 0 ? row : 0) * D) + g;
-    const float* qp = q + (int64_t)qi * D;
+// fma(acc_lo, 1 / kLoScale, acc).
+__device__ inline float rescore_chain(const float* __restrict__ q, const _Float16* __restrict__ x_row, int D, int n, int g) {
+    const f16x8* xp = reinterpret_cast<const f16x8*>(x_row) + g;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_lo = {0.f, 0.f, 0.f, 0.f};
     for (int j = 0; j < D / 32; ++j) {
         const f16x8 x = xp[j * 4];
         f16x8 ah, al;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {  // the split of k_query_fragments_f16
-            const float v = n == 0 ? qp[32 * j + 8 * g + e] : 0.f;
+            const float v = n == 0 ? q[32 * j + 8 * g + e] : 0.f;
             const _Float16 h = (_Float16)v;
             ah[e] = h;
             al[e] = (_Float16)((v - (float)h) * kLoScale);
@@ -926,14 +917,41 @@ __global__ __launch_bounds__(256) void k_gt_rescore_f16(const float* __restrict_
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, x, acc, 0, 0, 0);
         acc_lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, x, acc_lo, 0, 0, 0);
     }
+    return fmaf(acc_lo[0], 1.0f / kLoScale, acc[0]);
+}
+
+// exact[qi][c] = chain(q[qi], idx[ids[qi * id_stride + c]]) * row_scale for c < kk, -inf where the list has no entry:
+// beyond cand_cnt[qi] when a count is given (the GEMM path's int32 lists), else where the id is negative (the
+// two-stage path's int64 lists, padded with -1).
+template <class RowT, class IdT>
+__global__ __launch_bounds__(256) void k_rescore(const float* __restrict__ q, int D, const RowT* __restrict__ idx,
+                                                 const float* __restrict__ row_scale, const IdT* __restrict__ ids, int id_stride,
+                                                 const int32_t* __restrict__ cand_cnt, int Q, int kk,
+                                                 float* __restrict__ exact /* [Q, kk] */) {
+    const int lane = threadIdx.x & 63;
+    const int n = lane & 15, g = lane >> 4;
+    const int tiles = (kk + 15) / 16;
+    const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (w >= (int64_t)Q * tiles) return;  // whole waves only: the MFMAs below run with all 64 lanes
+    const int qi = (int)(w / tiles), t = (int)(w % tiles);
+    const int m = cand_cnt && cand_cnt[qi * kCntStride] < kk ? cand_cnt[qi * kCntStride] : kk;
+    const int c = t * 16 + n;
+    const IdT row = c < m ? ids[(int64_t)qi * id_stride + c] : -1;
+    const float dot = rescore_chain(q + (int64_t)qi * D, idx + (int64_t)(row >= 0 ? row : 0) * D, D, n, g);
     if (g == 0 && c < kk) {
         float s = -INFINITY;
-        if (row >= 0) {
-            const float dot = fmaf(acc_lo[0], 1.0f / kLoScale, acc[0]);
-            s = row_scale ? dot * row_scale[row] : dot;
-        }
+        if (row >= 0) s = row_scale ? dot * row_scale[row] : dot;
         exact[(int64_t)qi * kk + c] = s;
     }
+}
+
+template <class RowT, class IdT>
+static void launch_rescore(int timing_class, hipStream_t st, const float* q, int D, const void* idx, const float* row_scale,
+                           const IdT* ids, int id_stride, const int32_t* cand_cnt, int Q, int kk, float* exact) {
+    const int tiles = (kk + 15) / 16;
+    const int64_t waves = (int64_t)Q * tiles;
+    launch_timed(timing_class, k_rescore<RowT, IdT>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, q, D,
+                 static_cast<const RowT*>(idx), row_scale, ids, id_stride, cand_cnt, Q, kk, exact);
 }
 
 // final selection on the exact scores: (score desc, row id asc), like the scan
@@ -948,16 +966,7 @@ __global__ __launch_bounds__(kSelectThreads) void k_gt_final(const float* __rest
     const int32_t* ci = cand_id + (int64_t)qi * kGemmTopkCap;
     auto load = [&](int64_t i) -> uint64_t { return make_key(es[i], (uint32_t)ci[i]); };
     const int m = block_topk(sh, load, m0, k);
-    for (int i = threadIdx.x; i < k; i += blockDim.x) {
-        if (i < m) {
-            const uint64_t key = sh.keys[i];
-            out_score[(int64_t)qi * k + i] = key_score(key);
-            out_index[(int64_t)qi * k + i] = row_id_base + (int64_t)key_index(key);
-        } else {
-            out_score[(int64_t)qi * k + i] = -INFINITY;
-            out_index[(int64_t)qi * k + i] = -1;
-        }
-    }
+    write_topk(sh, m, qi, k, row_id_base, out_score, out_index);
 }
 
 struct GtLayout {
@@ -1077,14 +1086,10 @@ static int cosine_topk_gemm_impl(const float* q, int Q, const void* idx, int f16
         seg = next < L.slab ? next : L.slab;
     }
     hipLaunchKernelGGL(k_gt_gap, dim3(Q), dim3(64), 0, st, q, Q, D, cs, cnt, k, kk, single ? kApproxEps1 : kApproxEps, status);
-    const int tiles = (kk + 15) / 16;
-    const int64_t waves = (int64_t)Q * tiles;
     if (f16)
-        hipLaunchKernelGGL(k_gt_rescore_f16, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, q, D,
-                           static_cast<const _Float16*>(idx), row_scale, ci, cnt, Q, kk, exact);
+        launch_rescore<_Float16>(kUntimed, st, q, D, idx, row_scale, ci, kGemmTopkCap, cnt, Q, kk, exact);
     else
-        hipLaunchKernelGGL(k_gt_rescore, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, q, D, static_cast<const float*>(idx),
-                           row_scale, ci, cnt, Q, kk, exact);
+        launch_rescore<float>(kUntimed, st, q, D, idx, row_scale, ci, kGemmTopkCap, cnt, Q, kk, exact);
     hipLaunchKernelGGL(k_gt_final, dim3(Q), dim3(kSelectThreads), 0, st, exact, ci, cnt, kk, k, row_id_base, out_score,
                        out_index);
     EVI_LAUNCH_CHECK();
@@ -1147,44 +1152,6 @@ __global__ void k_shadow_f16(const float* __restrict__ x, int64_t n, _Float16* _
         out[i] = (_Float16)x[i];
 }
 
-// k_gt_rescore for [Q, kk] i64 candidate ids (-1 = padding): one wave per (query, 16 candidates)
-__global__ __launch_bounds__(256) void k_ts_rescore(const float* __restrict__ q, int D, const float* __restrict__ idx,
-                                                    const int64_t* __restrict__ ids, int Q, int kk,
-                                                    float* __restrict__ exact /* [Q, kk] */) {
-    const int lane = threadIdx.x & 63;
-    const int n = lane & 15, g = lane >> 4;
-    const int tiles = (kk + 15) / 16;
-    const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (w >= (int64_t)Q * tiles) return;  // whole waves only: the MFMAs below run with all 64 lanes
-    const int qi = (int)(w / tiles), t = (int)(w % tiles);
-    const int c = t * 16 + n;
-    const int64_t row = c < kk ? ids[(int64_t)qi * kk + c] : -1;
-    const f32x4* xp = reinterpret_cast<const f32x4*>(idx + (row >= 0 ? row : 0) * D) + g;
-    const f32x4* qp = reinterpret_cast<const f32x4*>(q + (int64_t)qi * D) + g;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    // eight 64-byte pieces of the row in flight per lane group: the rows are scattered over the index, so a loop that
-    // waits for each piece is bound by the HBM latency (48 round trips at D = 768); the MFMA order is unchanged
-    constexpr int PF = 8;
-    const int J = D / 16;
-    for (int j0 = 0; j0 < J; j0 += PF) {
-        f32x4 x[PF], a[PF];
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {  // unconditional loads (a piece past the end re-reads the last one): a bounds
-            const int j = j0 + u < J ? j0 + u : J - 1;  // branch here would make the compiler wait for each load in turn
-            x[u] = xp[j * 4];
-            a[u] = n == 0 ? qp[j * 4] : zero;
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u)
-            if (j0 + u < J) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][e], x[u][e], acc, 0, 0, 0);
-            }
-    }
-    if (g == 0 && c < kk) exact[(int64_t)qi * kk + c] = row >= 0 ? acc[0] : -INFINITY;
-}
-
 // Final top-k on the exact scores, and the proof: approx / ids are the [Q, kk] lists evi_cosine_topk_f16 wrote (sorted,
 // (-inf, -1) past the end of a short index); the true top-k is among them when approx[k-1] - approx[kk-1] > 2 eps |q|.
 __global__ __launch_bounds__(kSelectThreads) void k_ts_final(const float* __restrict__ exact, const int64_t* __restrict__ ids,
@@ -1196,20 +1163,16 @@ __global__ __launch_bounds__(kSelectThreads) void k_ts_final(const float* __rest
     const int qi = blockIdx.x;
     const float* es = exact + (int64_t)qi * kk;
     const int64_t* ci = ids + (int64_t)qi * kk;
-    if (threadIdx.x < 64) {  // wave 0: |q|^2 in a fixed order, then the gap test
+    if (threadIdx.x < 64) {  // wave 0: the gap test
         const int lane = threadIdx.x;
-        float ss = 0.f;
-        for (int d = lane; d < D; d += 64) ss = fmaf(q[(int64_t)qi * D + d], q[(int64_t)qi * D + d], ss);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+        const float ss = wave_sumsq(q + (int64_t)qi * D, D, lane);
         if (lane == 0 && ci[kk - 1] >= 0) {  // otherwise every row of the index is in the list
             const float* s = approx + (int64_t)qi * kk;
-            const float gap = s[k - 1] - s[kk - 1];
             // the bound is relative to |q| and assumes the f16 hi / lo split of the query keeps its 22 bits: far from unit
             // norm (elements near the f16 subnormal range, or the 2048 x lo part near overflow) it does not hold, and the
             // proof is refused — the f32 scan then does the batch
             const bool norm_ok = ss >= 0.0625f && ss <= 16.0f;
-            if (!(gap > 2.0f * eps * sqrtf(ss)) || !norm_ok) {  // also catches NaN scores
+            if (gap_fails(s[k - 1] - s[kk - 1], eps, ss) || !norm_ok) {  // also catches NaN scores
                 if (status) atomicOr(status, 1);  // the caller's sticky flag (a pipeline of batches shares it)
                 atomicOr(call_flag, 1);           // this call's own flag: opens the gate of the fallback scan
             }
@@ -1217,16 +1180,7 @@ __global__ __launch_bounds__(kSelectThreads) void k_ts_final(const float* __rest
     }
     auto load = [&](int64_t i) -> uint64_t { return ci[i] >= 0 ? make_key(es[i], (uint32_t)ci[i]) : 0ull; };
     const int m = block_topk(sh, load, kk, k);
-    for (int i = threadIdx.x; i < k; i += blockDim.x) {
-        const uint64_t key = i < m ? sh.keys[i] : 0ull;
-        if (key != 0ull) {
-            out_score[(int64_t)qi * k + i] = key_score(key);
-            out_index[(int64_t)qi * k + i] = row_id_base + (int64_t)key_index(key);
-        } else {
-            out_score[(int64_t)qi * k + i] = -INFINITY;
-            out_index[(int64_t)qi * k + i] = -1;
-        }
-    }
+    write_topk(sh, m, qi, k, row_id_base, out_score, out_index);
 }
 
 struct TsLayout {
@@ -1288,31 +1242,19 @@ extern "C" int evi_cosine_topk_two_stage(const float* q, int Q, const float* idx
     int32_t* call_flag = reinterpret_cast<int32_t*>(base + L.flag);
     EVI_HIP_CHECK(hipMemsetAsync(call_flag, 0, sizeof(int32_t), st));
     // stage 1: kk best rows per query by shadow score (local row ids)
-    const int rc = cosine_topk_impl(q, Q, shadow_f16, 1, N, D, nullptr, kk, 0, approx, ids, base + L.scan, L.scan_bytes, stream);
+    const int rc = cosine_topk_impl(q, Q, shadow_f16, kIdxF16, N, D, nullptr, kk, 0, approx, ids, base + L.scan, L.scan_bytes, stream);
     if (rc != EVI_OK) return rc;
     // stage 2: exact scores from the f32 rows, final top-k + proof
-    const int tiles = (kk + 15) / 16;
-    const int64_t waves = (int64_t)Q * tiles;
-    hipEvent_t e0, e1;
-    if (timing_kernel_events(kTimeSelect, &e0, &e1))
-        hipExtLaunchKernelGGL(k_ts_rescore, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, e0, e1, 0, q, D, idx,
-                              (const int64_t*)ids, Q, kk, exact);
-    else
-        hipLaunchKernelGGL(k_ts_rescore, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, q, D, idx, ids, Q, kk, exact);
-    if (timing_kernel_events(kTimeSelect, &e0, &e1))
-        hipExtLaunchKernelGGL(k_ts_final, dim3(Q), dim3(kSelectThreads), 0, st, e0, e1, 0, (const float*)exact,
-                              (const int64_t*)ids, kk, k, row_id_base, out_score, out_index, q, D, (const float*)approx,
-                              kShadowEps, status, call_flag);
-    else
-        hipLaunchKernelGGL(k_ts_final, dim3(Q), dim3(kSelectThreads), 0, st, exact, ids, kk, k, row_id_base, out_score, out_index,
-                           q, D, approx, kShadowEps, status, call_flag);
+    launch_rescore<float>(kTimeSelect, st, q, D, idx, nullptr, ids, kk, nullptr, Q, kk, exact);
+    launch_timed(kTimeSelect, k_ts_final, dim3(Q), dim3(kSelectThreads), 0, st, exact, ids, kk, k, row_id_base, out_score,
+                 out_index, q, D, approx, kShadowEps, status, call_flag);
     EVI_LAUNCH_CHECK();
     if (device_fallback) {
         // The f32 scan of the same batch into the same outputs, gated on this call's flag: while the proof held every
         // kernel returns at once (a few empty launches); when it failed the scan overwrites the unproven result before any
         // later work of the stream can read it.  No read-back, no agreement between ranks needed: each shard's record is
         // exact when it leaves the device.  The stage-1 scan workspace is free again and large enough (kk >= k).
-        const int rc2 = cosine_topk_impl(q, Q, idx, 0, N, D, nullptr, k, row_id_base, out_score, out_index, base + L.scan,
+        const int rc2 = cosine_topk_impl(q, Q, idx, kIdxF32, N, D, nullptr, k, row_id_base, out_score, out_index, base + L.scan,
                                          L.scan_bytes, stream, call_flag);
         if (rc2 != EVI_OK) return rc2;
     }

@@ -50,6 +50,42 @@ def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def _nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+def _reserve_fits(k: int) -> bool:
+    """k + reserve candidates of the GEMM-shaped and two-stage paths fit one selection (EVI_TOPK_MAX_K)."""
+    return k + max(256, k // 2) <= 2048
+
+
+def _topk_operands(queries: torch.Tensor, index: torch.Tensor, row_scale: Optional[torch.Tensor]):
+    """(queries, index, row_scale) as the top-k entry points take them: 2-D and contiguous, queries f32 [Q, D], index
+    [N, D] f32 or kept in its uint8 (e4m3) / float16 storage, row_scale f32 [N] or None."""
+    if queries.dim() != 2 or index.dim() != 2:
+        raise ValueError("queries and index must be 2D")
+    q = _f32c(queries, "queries")
+    x = index.contiguous() if index.dtype in (torch.float16, torch.uint8) else _f32c(index, "index")
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"query dim {q.shape[1]} != index dim {x.shape[1]}")
+    if row_scale is not None:
+        row_scale = _f32c(row_scale, "row_scale").view(-1)
+        if row_scale.numel() != x.shape[0]:
+            raise ValueError(f"row_scale length {row_scale.numel()} != N {x.shape[0]}")
+    return q, x, row_scale
+
+
+def _topk_out(out: Optional[Tuple[torch.Tensor, torch.Tensor]], Q: int, k: int, dev: torch.device):
+    """The caller's validated out=(scores, ids) pair, or freshly allocated tensors."""
+    if out is None:
+        return torch.empty((Q, k), dtype=torch.float32, device=dev), torch.empty((Q, k), dtype=torch.int64, device=dev)
+    out_score, out_index = out
+    if (out_score.shape != (Q, k) or out_index.shape != (Q, k) or out_score.dtype != torch.float32
+            or out_index.dtype != torch.int64 or not out_score.is_contiguous() or not out_index.is_contiguous()):
+        raise ValueError("out must be contiguous (float32 [Q, k], int64 [Q, k]) tensors")
+    return out_score, out_index
+
+
 def _workspace(dev: torch.device, tag: str, nbytes: int) -> torch.Tensor:
     """Grow-only per-(device, tag) scratch buffer (mirrors the reference's grow-only pinned
     buffers, src/data/components/embedding_store.py:101-150, but in HBM)."""
@@ -168,50 +204,29 @@ def cosine_topk(
     if method not in ("scan", "gemm", "auto"):
         raise ValueError(f"method must be 'scan', 'gemm' or 'auto', got {method!r}")
     if method != "scan" and index.dtype in (torch.float32, torch.float16) and queries.dim() == 2 and index.dim() == 2:
-        eligible = index.size(1) % (32 if index.dtype == torch.float16 else 16) == 0 and k + max(256, k // 2) <= 2048 and index.size(0) >= 1 and queries.size(0) >= 1
+        eligible = index.size(1) % (32 if index.dtype == torch.float16 else 16) == 0 and _reserve_fits(k) and index.size(0) >= 1 and queries.size(0) >= 1
         if method == "gemm" or (eligible and queries.size(0) >= 96):
             cosine_topk.last_method = "gemm"
             return cosine_topk_gemm(queries, index, k, row_scale=row_scale, row_id_base=row_id_base, out=out)
         shadow = resident_shadow_f16(index) if (method == "auto" and row_scale is None and index.dtype == torch.float32) else None
-        if shadow is not None and queries.size(0) >= 1 and index.size(0) >= 1 and k + max(256, k // 2) <= 2048 and index.size(1) % 32 == 0 \
+        if shadow is not None and queries.size(0) >= 1 and index.size(0) >= 1 and _reserve_fits(k) and index.size(1) % 32 == 0 \
                 and queries.dtype == torch.float32 and queries.size(1) == index.size(1):
             cosine_topk.last_method = "two_stage"
             return cosine_topk_two_stage(queries, index, shadow, k, row_id_base=row_id_base, out=out, fallback="device")
     cosine_topk.last_method = "scan"
     dev = _require_gpu(queries, index, row_scale, workspace)
-    if queries.dim() != 2 or index.dim() != 2:
-        raise ValueError("queries and index must be 2D")
-    q = _f32c(queries, "queries")
-    if index.dtype == torch.float16:
-        x = index.contiguous()  # f16-storage index: evi_cosine_topk_f16
-    elif index.dtype == torch.uint8:
-        x = index.contiguous()  # e4m3 bytes from quantize_rows_fp8: evi_cosine_topk_fp8 (row_scale required)
-        if row_scale is None:
-            raise ValueError("an fp8 index needs row_scale (the per-row scale returned by quantize_rows_fp8)")
-    else:
-        x = _f32c(index, "index")
+    if index.dim() == 2 and index.dtype == torch.uint8 and row_scale is None:  # e4m3 bytes from quantize_rows_fp8
+        raise ValueError("an fp8 index needs row_scale (the per-row scale returned by quantize_rows_fp8)")
+    q, x, row_scale = _topk_operands(queries, index, row_scale)  # f16 / uint8 storage: evi_cosine_topk_f16 / _fp8
     Q, D = q.shape
-    N, D2 = x.shape
-    if D != D2:
-        raise ValueError(f"query dim {D} != index dim {D2}")
-    if row_scale is not None:
-        row_scale = _f32c(row_scale, "row_scale").view(-1)
-        if row_scale.numel() != N:
-            raise ValueError(f"row_scale length {row_scale.numel()} != N {N}")
+    N = x.shape[0]
     if Q == 0:
         return (torch.empty((0, k), dtype=torch.float32, device=dev), torch.empty((0, k), dtype=torch.int64, device=dev))
     lib = _lib.load()
     need = int(lib.evi_cosine_topk_workspace_bytes(Q, N, D, int(k)))
     if workspace is None:
         workspace = _workspace(dev, "cosine_topk", need)
-    if out is not None:
-        out_score, out_index = out
-        if (out_score.shape != (Q, k) or out_index.shape != (Q, k) or out_score.dtype != torch.float32
-                or out_index.dtype != torch.int64 or not out_score.is_contiguous() or not out_index.is_contiguous()):
-            raise ValueError("out must be contiguous (float32 [Q, k], int64 [Q, k]) tensors")
-    else:
-        out_score = torch.empty((Q, k), dtype=torch.float32, device=dev)
-        out_index = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    out_score, out_index = _topk_out(out, Q, k, dev)
     if fp8_mfma and x.dtype != torch.uint8:
         raise ValueError("fp8_mfma goes with an e4m3 (uint8) index")
     if fp8_mfma is None:
@@ -221,7 +236,7 @@ def cosine_topk(
     _lib.check(
         fn(
             _ptr(q), Q, _ptr(x), N, D, _ptr(row_scale), int(k), int(row_id_base),
-            _ptr(out_score), _ptr(out_index), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+            _ptr(out_score), _ptr(out_index), workspace.data_ptr(), _nbytes(workspace),
             _stream(dev),
         )
     )
@@ -317,18 +332,11 @@ def cosine_topk_gemm(queries: torch.Tensor, index: torch.Tensor, k: int, *, row_
         if index.dtype != torch.float32 or shadow.dtype != torch.bfloat16 or shadow.shape != index.shape or not shadow.is_contiguous():
             raise ValueError("shadow must be the contiguous bfloat16 copy of an f32 index (index_shadow_bf16)")
     dev = _require_gpu(queries, index, row_scale)
-    if queries.dim() != 2 or index.dim() != 2:
-        raise ValueError("queries and index must be 2D")
-    q = _f32c(queries, "queries")
-    x = index.contiguous() if index.dtype == torch.float16 else _f32c(index, "index")  # f16 storage: evi_cosine_topk_gemm_f16
+    if index.dtype == torch.uint8:
+        raise ValueError(f"index must be float32 or float16, got {index.dtype}")
+    q, x, row_scale = _topk_operands(queries, index, row_scale)  # f16 storage: evi_cosine_topk_gemm_f16
     Q, D = q.shape
     N = x.shape[0]
-    if x.shape[1] != D:
-        raise ValueError(f"query dim {D} != index dim {x.shape[1]}")
-    if row_scale is not None:
-        row_scale = _f32c(row_scale, "row_scale").view(-1)
-        if row_scale.numel() != N:
-            raise ValueError(f"row_scale length {row_scale.numel()} != N {N}")
     if Q == 0 or N == 0:
         return cosine_topk(q, x, k, row_scale=row_scale, row_id_base=row_id_base, out=out, method="scan")
     # the proof's error bound is kApproxEps * |q| * |row|, with |row| <= 1 built in: an index of longer rows would pass
@@ -341,14 +349,7 @@ def cosine_topk_gemm(queries: torch.Tensor, index: torch.Tensor, k: int, *, row_
         return cosine_topk(q, x, k, row_scale=row_scale, row_id_base=row_id_base, out=out, method="scan")
     lib = _lib.load()
     ws = _workspace(dev, "cosine_topk_gemm", int(lib.evi_cosine_topk_gemm_workspace_bytes(Q, N, D, int(k))))
-    if out is not None:
-        out_score, out_index = out
-        if (out_score.shape != (Q, k) or out_index.shape != (Q, k) or out_score.dtype != torch.float32
-                or out_index.dtype != torch.int64 or not out_score.is_contiguous() or not out_index.is_contiguous()):
-            raise ValueError("out must be contiguous (float32 [Q, k], int64 [Q, k]) tensors")
-    else:
-        out_score = torch.empty((Q, k), dtype=torch.float32, device=dev)
-        out_index = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    out_score, out_index = _topk_out(out, Q, k, dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
     fn = lib.evi_cosine_topk_gemm_f16 if x.dtype == torch.float16 else lib.evi_cosine_topk_gemm
     # The single-product (plain bf16) selection keeps max(1024, k) reserve rows per query and needs the k-th and the last kept
@@ -432,12 +433,9 @@ def cosine_topk_two_stage(queries: torch.Tensor, index: torch.Tensor, shadow: to
         raise ValueError("queries and index must be 2D")
     if index.dtype != torch.float32 or shadow.dtype != torch.float16 or shadow.shape != index.shape or not shadow.is_contiguous():
         raise ValueError("shadow must be the contiguous float16 copy of an f32 index (index_shadow_f16)")
-    q = _f32c(queries, "queries")
-    x = _f32c(index, "index")
+    q, x, _ = _topk_operands(queries, index, None)
     Q, D = q.shape
     N = x.shape[0]
-    if x.shape[1] != D:
-        raise ValueError(f"query dim {D} != index dim {x.shape[1]}")
     # the exactness proof bounds the f16 rounding of a row by 2^-11 of its norm and assumes norm <= 1, like cosine_topk_gemm's:
     # the same guard (one pass over the index + one read-back the FIRST time this tensor is seen, cached on the tensor)
     if check_norms and N and not rows_are_unit_norm(x):
@@ -452,21 +450,14 @@ def cosine_topk_two_stage(queries: torch.Tensor, index: torch.Tensor, shadow: to
     if need == 0:
         raise ValueError(f"k + max(256, k // 2) must not exceed 2048, got k = {k}")
     ws = workspace if workspace is not None else _workspace(dev, "cosine_topk_two_stage", need)
-    if out is not None:
-        out_score, out_index = out
-        if (out_score.shape != (Q, k) or out_index.shape != (Q, k) or out_score.dtype != torch.float32
-                or out_index.dtype != torch.int64 or not out_score.is_contiguous() or not out_index.is_contiguous()):
-            raise ValueError("out must be contiguous (float32 [Q, k], int64 [Q, k]) tensors")
-    else:
-        out_score = torch.empty((Q, k), dtype=torch.float32, device=dev)
-        out_index = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    out_score, out_index = _topk_out(out, Q, k, dev)
     on_device = fallback == "device"
     flag = status
     if flag is None and not on_device:
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
     _lib.check(lib.evi_cosine_topk_two_stage(_ptr(q), Q, _ptr(x), _ptr(shadow), N, D, int(k), int(row_id_base), _ptr(out_score),
                                              _ptr(out_index), _ptr(flag), 1 if on_device else 0, ws.data_ptr(),
-                                             ws.numel() * ws.element_size(), _stream(dev)))
+                                             _nbytes(ws), _stream(dev)))
     if on_device or status is not None:
         return out_score, out_index
     st = int(flag.item())
@@ -514,16 +505,9 @@ def topk_merge_packed(packed: torch.Tensor, P: int, Q: int, k: int,
     dev = _require_gpu(packed)
     lib = _lib.load()
     rec = int(lib.evi_topk_packed_bytes(Q, k))
-    if packed.numel() * packed.element_size() < P * rec:
-        raise ValueError(f"packed buffer holds {packed.numel() * packed.element_size()} B, need {P * rec} B")
-    if out is not None:
-        out_score, out_index = out
-        if out_score.shape != (Q, k) or out_index.shape != (Q, k) or out_score.dtype != torch.float32 or \
-                out_index.dtype != torch.int64 or not out_score.is_contiguous() or not out_index.is_contiguous():
-            raise ValueError("out must be contiguous (f32 [Q, k], i64 [Q, k]) tensors")
-    else:
-        out_score = torch.empty((Q, k), dtype=torch.float32, device=dev)
-        out_index = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    if _nbytes(packed) < P * rec:
+        raise ValueError(f"packed buffer holds {_nbytes(packed)} B, need {P * rec} B")
+    out_score, out_index = _topk_out(out, Q, k, dev)
     _lib.check(lib.evi_topk_merge_packed(packed.data_ptr(), P, Q, k, _ptr(out_score), _ptr(out_index), _stream(dev)))
     return out_score, out_index
 
@@ -624,12 +608,12 @@ def graph_csr(edge_index: torch.Tensor, node_ptr: torch.Tensor, edge_ptr: torch.
         raise ValueError("out: CSR buffers too small for this batch")
     lib = _lib.load()
     need = int(lib.evi_graph_csr_workspace_bytes(N))
-    if workspace is not None and workspace.numel() * workspace.element_size() < need:
-        raise ValueError(f"workspace holds {workspace.numel() * workspace.element_size()} B, need {need} B")
+    if workspace is not None and _nbytes(workspace) < need:
+        raise ValueError(f"workspace holds {_nbytes(workspace)} B, need {need} B")
     ws = workspace if workspace is not None else _workspace(dev, "graph_csr", need)
     _lib.check(lib.evi_graph_csr(_ptr(ei), E, _ptr(ptr), _ptr(eptr), B, N, csr.in_ptr.data_ptr(), csr.in_nbr.data_ptr(),
                                  csr.in_eid.data_ptr(), csr.out_ptr.data_ptr(), csr.out_nbr.data_ptr(),
-                                 csr.out_eid.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream(dev)))
+                                 csr.out_eid.data_ptr(), ws.data_ptr(), _nbytes(ws), _stream(dev)))
     return csr
 
 

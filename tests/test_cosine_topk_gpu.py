@@ -408,7 +408,10 @@ def test_reduced_precision_index_at_shard_size(dev, storage):
 
 
 @pytest.mark.parametrize("Q,N,D,k,scaled", [(512, 400000, 768, 500, False), (130, 50000, 128, 100, True), (96, 3000, 64, 10, False),
-                                             (64, 700, 32, 500, False)])
+                                             (64, 700, 32, 500, False),
+                                             # D/16 = 9 and 17: the re-score chain's clamped prefetch tail; kk = 266: a partly
+                                             # filled last candidate tile; N < kk: the count-limited lists
+                                             (96, 2000, 144, 10, False), (33, 1200, 272, 10, True), (96, 200, 144, 10, False)])
 def test_cosine_topk_gemm_equals_scan_bit_for_bit(dev, Q, N, D, k, scaled):
     """Many-query path: ids AND scores identical to the scan (its candidates are re-scored with the scan's own
     MFMA sequence); duplicated rows (exact ties) and a zero row are in the index."""
@@ -457,7 +460,8 @@ def test_cosine_topk_gemm_refuses_what_it_cannot_prove(dev):
         ops.cosine_topk_gemm(qn, idx, 1100, products=1)  # the coarse selection needs k + 1100 > 2048 slots
 
 
-@pytest.mark.parametrize("Q,N,D,k", [(256, 300000, 768, 500), (100, 20000, 64, 40)])
+@pytest.mark.parametrize("Q,N,D,k", [(256, 300000, 768, 500), (100, 20000, 64, 40),
+                                     (96, 2000, 96, 10), (96, 200, 96, 10)])  # three 32-wide chunks; a short list
 def test_cosine_topk_gemm_f16_index_equals_f16_scan(dev, Q, N, D, k):
     """f16-stored index: the many-query path must reproduce evi_cosine_topk_f16 bit for bit."""
     from evi_rag_amd import ops
@@ -475,7 +479,8 @@ def test_cosine_topk_gemm_f16_index_equals_f16_scan(dev, Q, N, D, k):
 
 
 @pytest.mark.parametrize("Q,N,D,k", [(32, 400000, 768, 500), (33, 70000, 768, 500), (7, 3000, 64, 10), (32, 600, 32, 500),
-                                     (1, 1, 32, 1), (40, 100000, 384, 100), (16, 1 << 20, 128, 1365)])
+                                     (1, 1, 32, 1), (40, 100000, 384, 100), (16, 1 << 20, 128, 1365),
+                                     (5, 2000, 416, 10), (5, 200, 416, 10)])  # D/16 = 26: prefetch tail; -1 padded ids
 def test_cosine_topk_two_stage_equals_scan_bit_for_bit(dev, Q, N, D, k):
     """f16-shadow selection + f32 re-scoring: ids AND scores identical to the f32 scan; the index holds duplicated rows
     (exact ties), a zero row, and (N < k + reserve cases) fewer rows than the candidate list."""

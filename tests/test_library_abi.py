@@ -98,3 +98,28 @@ def test_topk_workspace_sizes_are_pinned(shape, want):
     lib = _lib.load()
     got = (lib.evi_cosine_topk_gemm_workspace_bytes(*shape), lib.evi_cosine_topk_two_stage_workspace_bytes(*shape))
     assert got == want
+
+
+# (Q, N, D, k) -> scan workspace, minimum scan workspace, GEMM top-k workspace, two-stage workspace, packed record: the values
+# of the build before the scan's layout moved onto Bump (shapes of the bit-for-bit tests' odd-D cases and the two bench shapes)
+_TOPK_ALL_SIZES = [
+    ((96, 2000, 144, 10), (541440, 541440, 13834496, 1015808, 11520)),
+    ((33, 1200, 272, 10), (353024, 353024, 4667648, 559872, 3960)),
+    ((96, 200, 144, 10), (80640, 80640, 13143296, 555008, 11520)),
+    ((96, 2000, 96, 10), (535296, 535296, 13809920, 1009664, 11520)),
+    ((96, 200, 96, 10), (74496, 74496, 13118720, 548864, 11520)),
+    ((5, 2000, 416, 10), (576256, 576256, 726528, 663552, 600)),
+    ((5, 200, 416, 10), (115456, 115456, 690432, 202752, 600)),
+    ((32, 1 << 23, 768, 500), (2147718400, 17011968, 5020416, 2148171264, 192000)),
+    ((512, 400000, 768, 500), (102634752, 17011968, 80324608, 108893696, 3072000)),
+]
+
+
+@pytest.mark.parametrize("shape,want", _TOPK_ALL_SIZES)
+def test_topk_size_functions_are_pinned(shape, want):
+    lib = _lib.load()
+    Q, _, _, k = shape
+    got = (lib.evi_cosine_topk_workspace_bytes(*shape), lib.evi_cosine_topk_min_workspace_bytes(*shape),
+           lib.evi_cosine_topk_gemm_workspace_bytes(*shape), lib.evi_cosine_topk_two_stage_workspace_bytes(*shape),
+           lib.evi_topk_packed_bytes(Q, k))
+    assert got == want
