@@ -107,7 +107,10 @@ int launch_gemm_tn_bf16x3(const float* A, int64_t lda, int M, const float* B, in
 int launch_gemm_nt_bf16x3_splitk(const float* A, int64_t M, int64_t Ktot, int64_t lda, const float* W, int N, int64_t ldw, int Ks,
                                  int S, float* Cparts, void* wsplit, hipStream_t st);
 int split_weight_bf16x3(const float* W, int N, int K, int64_t ldw, void* wsplit, hipStream_t st);
-// a_f16: 0 = A is f32, 1 = A stored as f16, 2 = A is a bf16 copy (implies single);
+// the hi / lo planes inside `wsplit` ([N, Kp] bf16 each, zero padded to Kp) for a caller that writes them itself
+void bf16x3_planes(void* wsplit, int N, int K, __bf16** hi, __bf16** lo, int* Kp);
+// a_f16: 0 = A is f32, 1 = A stored as f16, 2 = A is a bf16 copy (implies single), 3 = A is e4m3 bytes (lda in bytes; two
+//        products, `single` must be 0);
 // single: one product (hi * hi, plain bf16 accuracy) instead of three
 int launch_gemm_bf16x3_filter(const void* A, int a_f16, int single, int64_t M, int K, int64_t lda, const void* wsplit, int N,
                               const GemmFilter& flt, hipStream_t st);

@@ -159,6 +159,43 @@ __device__ inline float pow2_scale_for(float amax) {  // smallest power of two s
     frexpf(amax / 448.0f, &e);  // amax / 448 = f * 2^e, f in [0.5, 1)
     return ldexpf(1.0f, e);
 }
+// THE two-piece form of a query, in one place: the fragment kernel of the native scan, the query planes of the many-query
+// selection and the re-scoring chain all take a query's pieces and scales from these three functions, so they agree bit
+// for bit.  A maximum does not depend on the order it is taken in, so `reduce_max` may be a workgroup's or a wave's.
+__device__ inline uint32_t fp8n_piece1(float v, float s1) {
+    return (uint32_t)__hip_cvt_float_to_fp8(v / s1, __HIP_SATFINITE, __HIP_E4M3) & 0xFF;
+}
+__device__ inline float fp8n_residual(float v, float s1, uint32_t b1) { return v - s1 * e4m3_to_float(b1); }
+__device__ inline uint32_t fp8n_piece2(float v, float s1, uint32_t b1, float s2) {
+    return (uint32_t)__hip_cvt_float_to_fp8(fp8n_residual(v, s1, b1) / s2, __HIP_SATFINITE, __HIP_E4M3) & 0xFF;
+}
+// s1, s2 of the query row q[0 .. D) (all zeros when !live), elements first, first + step, ... per caller thread
+template <class ReduceMax>
+__device__ inline void fp8n_query_scales(const float* __restrict__ q, int D, bool live, int first, int step,
+                                         ReduceMax reduce_max, float& s1, float& s2) {
+    float a1 = 0.f;
+    for (int d = first; d < D; d += step) a1 = fmaxf(a1, live ? fabsf(q[d]) : 0.f);
+    s1 = pow2_scale_for(reduce_max(a1));
+    float a2 = 0.f;
+    for (int d = first; d < D; d += step) {
+        const float v = live ? q[d] : 0.f;
+        a2 = fmaxf(a2, fabsf(fp8n_residual(v, s1, fp8n_piece1(v, s1))));
+    }
+    s2 = pow2_scale_for(reduce_max(a2));
+}
+// maximum over a 256-thread workgroup through red[256]
+__device__ inline float block256_max(float* red, int tid, float v) {
+    red[tid] = v;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) red[tid] = fmaxf(red[tid], red[tid + off]);
+        __syncthreads();
+    }
+    const float m = red[0];
+    __syncthreads();
+    return m;
+}
+
 __global__ __launch_bounds__(256) void k_query_fragments_fp8n(const float* __restrict__ q, int Q, int D, int nq_pad,
                                                               uint64_t* __restrict__ qfrag, float* __restrict__ tau,
                                                               int32_t* __restrict__ cnt, const int32_t* __restrict__ gate) {
@@ -167,28 +204,9 @@ __global__ __launch_bounds__(256) void k_query_fragments_fp8n(const float* __res
     __shared__ float red[256];
     const int i = blockIdx.x, tid = threadIdx.x;  // one workgroup per query slot (grid = nq_pad)
     float* qscale = reinterpret_cast<float*>(reinterpret_cast<char*>(qfrag) + (size_t)D * 2 * nq_pad);
-    auto block_max = [&](float v) -> float {
-        red[tid] = v;
-        __syncthreads();
-        for (int off = 128; off > 0; off >>= 1) {
-            if (tid < off) red[tid] = fmaxf(red[tid], red[tid + off]);
-            __syncthreads();
-        }
-        const float m = red[0];
-        __syncthreads();
-        return m;
-    };
     const bool live = i < Q;
-    float a1 = 0.f;
-    for (int d = tid; d < D; d += 256) a1 = fmaxf(a1, live ? fabsf(q[(int64_t)i * D + d]) : 0.f);
-    const float s1 = pow2_scale_for(block_max(a1));
-    float a2 = 0.f;
-    for (int d = tid; d < D; d += 256) {
-        const float v = live ? q[(int64_t)i * D + d] : 0.f;
-        const uint32_t b1 = (uint32_t)__hip_cvt_float_to_fp8(v / s1, __HIP_SATFINITE, __HIP_E4M3);
-        a2 = fmaxf(a2, fabsf(v - s1 * e4m3_to_float(b1)));
-    }
-    const float s2 = pow2_scale_for(block_max(a2));
+    float s1, s2;
+    fp8n_query_scales(q + (int64_t)i * D, D, live, tid, 256, [&](float v) { return block256_max(red, tid, v); }, s1, s2);
     if (tid == 0) {
         qscale[i] = s1;
         qscale[kQueryBlock + i] = s2;
@@ -201,9 +219,8 @@ __global__ __launch_bounds__(256) void k_query_fragments_fp8n(const float* __res
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float v = live ? q[(int64_t)i * D + 64 * J + 16 * g + 8 * m + e] : 0.f;
-            const uint32_t b1 = (uint32_t)__hip_cvt_float_to_fp8(v / s1, __HIP_SATFINITE, __HIP_E4M3) & 0xFF;
-            const float r = v - s1 * e4m3_to_float(b1);
-            const uint32_t b2 = (uint32_t)__hip_cvt_float_to_fp8(r / s2, __HIP_SATFINITE, __HIP_E4M3) & 0xFF;
+            const uint32_t b1 = fp8n_piece1(v, s1);
+            const uint32_t b2 = fp8n_piece2(v, s1, b1, s2);
             w1 |= (uint64_t)b1 << (8 * e);
             w2 |= (uint64_t)b2 << (8 * e);
         }
@@ -788,6 +805,27 @@ constexpr float kApproxEps = 2.5e-4f;        // |gemm score - scan score| <= kAp
                                              // plus the scan's own 768 x 2^-24
 constexpr float kApproxEps1 = 4.2e-3f;       // single-product selection: both operands rounded to bf16 (2 x 2^-9 + 2^-18
                                              // relative per product), 768 accumulations, plus the scan's own error
+// e4m3 index (evi_cosine_topk_gemm_fp8), both scan variants: |selection score - scan score| <= kApproxEpsFp8Unit * |q| * |x|
+// for the STORED row x (codes x row_scale), D <= 1280, every f32 accumulation charged 2^-23 (truncating adders assumed,
+// as for kShadowEps).  Term by term, relative to |q| |x| (Cauchy-Schwarz on each sum):
+//   index side of the selection product                       0        an e4m3 code is exactly a bf16 value
+//   query of the selection, widening variant                  2^-16    f32 query as bf16 hi + lo, (2^-8)^2
+//   query of the scan, widening variant                       2^-22    f32 query as f16 hi + lo, (2^-11)^2
+//   query, native variant                                     0        selection and scan multiply the SAME two e4m3
+//                                                                      pieces; the power-of-two piece scales commute
+//                                                                      with every rounding
+//   selection GEMM: 2 products x D into one accumulator       2560 x 2^-23
+//   scan: D products into each of two accumulators            1280 x 2^-23   (the lo accumulator is <= 2^-8 of the hi one)
+//   combining fma of the scan, row_scale multiply on each side   3 x 2^-23
+//   sum: (2560 + 1280 + 3) x 2^-23 + 2^-16 + 2^-22 = 4.58e-4 + 1.55e-5 = 4.74e-4
+// The widening variant's query terms are relative to each element, which f16 grants only to queries of ordinary size:
+// the gap test refuses a query with |q| outside [1/4, 4] (as the two-stage path does) and the scan takes the batch.
+// Stored e4m3 rows are not unit norm: rounding to 4 significant bits moves each element by <= 2^-4 of itself, so a unit
+// row is stored with |x| <= 1 + 2^-4.  That is the tolerance the caller's norm check applies (kFp8RowNormMax); the proof
+// uses the product of the two.
+constexpr float kApproxEpsFp8Unit = 4.8e-4f;
+constexpr float kFp8RowNormMax = 1.0625f;
+constexpr float kApproxEpsFp8 = kApproxEpsFp8Unit * kFp8RowNormMax;  // 5.1e-4
 constexpr int kGemmTopkCap = 16384;          // candidate slots per query between two selections
 constexpr int64_t kGemmFirstRows = 4096;     // first slab: every row is a candidate (4096 <= cap)
 constexpr int64_t kGemmSlabRows = 1 << 21;   // rows per GEMM launch between two selections (bounds the appends)
@@ -851,8 +889,10 @@ __device__ inline float wave_sumsq(const float* __restrict__ q, int D, int lane)
 }
 __device__ inline bool gap_fails(float gap, float eps, float ss) { return !(gap > 2.0f * eps * sqrtf(ss)); }  // NaN fails too
 
+// q_norm_guard: the bound also needs |q| in [1/4, 4] (an f16 hi / lo split of the query is part of it)
 __global__ void k_gt_gap(const float* __restrict__ q, int Q, int D, const float* __restrict__ cand_score,
-                         const int32_t* __restrict__ cand_cnt, int k, int kk, float eps, int32_t* __restrict__ status) {
+                         const int32_t* __restrict__ cand_cnt, int k, int kk, float eps, int q_norm_guard,
+                         int32_t* __restrict__ status) {
     const int qi = blockIdx.x;
     const int lane = threadIdx.x;  // one wave
     const float ss = wave_sumsq(q + (int64_t)qi * D, D, lane);
@@ -860,7 +900,8 @@ __global__ void k_gt_gap(const float* __restrict__ q, int Q, int D, const float*
         const int m = cand_cnt[qi * kCntStride];
         if (m >= kk) {
             const float* s = cand_score + (int64_t)qi * kGemmTopkCap;
-            if (gap_fails(s[k - 1] - s[kk - 1], eps, ss)) atomicOr(status, 1);
+            const bool norm_ok = !q_norm_guard || (ss >= 0.0625f && ss <= 16.0f);
+            if (gap_fails(s[k - 1] - s[kk - 1], eps, ss) || !norm_ok) atomicOr(status, 1);
         }  // m < kk: every row of the index is in the list
     }
 }
@@ -918,6 +959,75 @@ __device__ inline float rescore_chain(const float* __restrict__ q, const _Float1
         acc_lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, x, acc_lo, 0, 0, 0);
     }
     return fmaf(acc_lo[0], 1.0f / kLoScale, acc[0]);
+}
+
+// An e4m3 index has two scan variants with different arithmetic, so a row pointer carries the variant as its type (one
+// byte per element either way).
+struct Fp8WidenRow { uint8_t code; };  // kIdxFp8Widen
+struct Fp8MfmaRow { uint8_t code; };   // kIdxFp8Mfma
+
+// kIdxFp8Widen: per 64-byte piece j lane group g owns bytes 16 g .. + 15, widened to f16 (value / 256) for two K-steps
+// m = 0, 1 of 8 bytes; the query is split f16 hi + lo as k_query_fragments_fp8 does; combine, then x 256.
+__device__ inline float rescore_chain(const float* __restrict__ q, const Fp8WidenRow* __restrict__ x_row, int D, int n, int g) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4* xp = reinterpret_cast<const u32x4*>(x_row) + g;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_lo = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < D / 64; ++j) {
+        const u32x4 w = xp[j * 4];
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            u32x4 h;
+            h[0] = fp8x2_to_f16x2_scaled(w[2 * m], 0x010C000Cu);
+            h[1] = fp8x2_to_f16x2_scaled(w[2 * m], 0x030C020Cu);
+            h[2] = fp8x2_to_f16x2_scaled(w[2 * m + 1], 0x010C000Cu);
+            h[3] = fp8x2_to_f16x2_scaled(w[2 * m + 1], 0x030C020Cu);
+            const f16x8 xb = __builtin_bit_cast(f16x8, h);
+            f16x8 ah, al;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {  // the split of k_query_fragments_fp8
+                const float v = n == 0 ? q[64 * j + 16 * g + 8 * m + e] : 0.f;
+                const _Float16 hv = (_Float16)v;
+                ah[e] = hv;
+                al[e] = (_Float16)((v - (float)hv) * kLoScale);
+            }
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xb, acc, 0, 0, 0);
+            acc_lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, xb, acc_lo, 0, 0, 0);
+        }
+    }
+    return fmaf(acc_lo[0], 1.0f / kLoScale, acc[0]) * 256.0f;
+}
+
+// kIdxFp8Mfma: the row's bytes as they are against the query's two e4m3 pieces (fp8n_*: what k_query_fragments_fp8n
+// writes), one accumulator per piece, combined as the scan's epilogue combines them.
+__device__ inline float rescore_chain(const float* __restrict__ q, const Fp8MfmaRow* __restrict__ x_row, int D, int n, int g) {
+    const int lane = g * 16 + n;
+    float s1, s2;
+    fp8n_query_scales(q, D, true, lane, 64, [](float v) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+        return v;
+    }, s1, s2);
+    const uint64_t* xp = reinterpret_cast<const uint64_t*>(x_row) + 2 * g;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc_lo = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < D / 64; ++j) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const long xb = (long)xp[j * 8 + m];
+            uint64_t w1 = 0, w2 = 0;
+            if (n == 0) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float v = q[64 * j + 16 * g + 8 * m + e];
+                    const uint32_t b1 = fp8n_piece1(v, s1);
+                    w1 |= (uint64_t)b1 << (8 * e);
+                    w2 |= (uint64_t)fp8n_piece2(v, s1, b1, s2) << (8 * e);
+                }
+            }
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8((long)w1, xb, acc, 0, 0, 0);
+            acc_lo = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8((long)w2, xb, acc_lo, 0, 0, 0);
+        }
+    }
+    return fmaf(acc_lo[0], s2, acc[0] * s1);
 }
 
 // exact[qi][c] = chain(q[qi], idx[ids[qi * id_stride + c]]) * row_scale for c < kk, -inf where the list has no entry:
@@ -1020,16 +1130,62 @@ extern "C" int evi_index_shadow_bf16(const float* idx, int64_t N, int D, void* o
     return EVI_OK;
 }
 
-static int cosine_topk_gemm_impl(const float* q, int Q, const void* idx, int f16, int products, const void* shadow, int64_t N,
+// Query planes of the many-query selection over an e4m3 index in its NATIVE scan variant: hi = s1 p1, lo = s2 p2, the two
+// dequantised pieces the scan multiplies (fp8n_*).  An e4m3 value times a power of two is exactly a bf16 value, so the
+// selection's ideal score equals the scan's and the two differ by accumulation order only.  One workgroup per query.
+__global__ __launch_bounds__(256) void k_fp8n_query_planes(const float* __restrict__ q, int D, int Kp, __bf16* __restrict__ hi,
+                                                           __bf16* __restrict__ lo) {
+    __shared__ float red[256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const float* qr = q + (int64_t)i * D;
+    float s1, s2;
+    fp8n_query_scales(qr, D, true, tid, 256, [&](float v) { return block256_max(red, tid, v); }, s1, s2);
+    for (int d = tid; d < Kp; d += 256) {
+        float p1 = 0.f, p2 = 0.f;
+        if (d < D) {
+            const uint32_t b1 = fp8n_piece1(qr[d], s1);
+            p1 = s1 * e4m3_to_float(b1);
+            p2 = s2 * e4m3_to_float(fp8n_piece2(qr[d], s1, b1, s2));
+        }
+        hi[(int64_t)i * Kp + d] = (__bf16)p1;
+        lo[(int64_t)i * Kp + d] = (__bf16)p2;
+    }
+}
+
+// the query planes the selection GEMM multiplies, in `wsplit`: the bf16 hi / lo split of the f32 query, or (native e4m3
+// variant) the scan's own two pieces
+static int gt_query_planes(IndexKind kind, const float* q, int Q, int D, void* wsplit, hipStream_t st) {
+    if (kind != kIdxFp8Mfma) return split_weight_bf16x3(q, Q, D, D, wsplit, st);  // the queries are the "weights": split once
+    __bf16 *hi, *lo;
+    int Kp;
+    bf16x3_planes(wsplit, Q, D, &hi, &lo, &Kp);
+    hipLaunchKernelGGL(k_fp8n_query_planes, dim3(Q), dim3(256), 0, st, q, D, Kp, hi, lo);
+    EVI_LAUNCH_CHECK();
+    return EVI_OK;
+}
+
+// scores [rows, Q] *= row_scale[row], as k_gt_filter scales them
+__global__ void k_gt_scale_rows(float* __restrict__ scores, int64_t rows, int Q, const float* __restrict__ row_scale) {
+    const int64_t total = rows * Q;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+        scores[i] *= row_scale[i / Q];
+}
+
+static int cosine_topk_gemm_impl(const float* q, int Q, const void* idx, IndexKind kind, int products, const void* shadow, int64_t N,
                                  int D, const float* row_scale, int k, int64_t row_id_base, float* out_score,
                                  int64_t* out_index, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
     EVI_REQUIRE(products == 1 || products == 3, "evi_cosine_topk_gemm: products must be 3 (split-bf16) or 1 (plain bf16), got %d",
                 products);
     const int single = products == 1;
-    EVI_REQUIRE(!shadow || (single && !f16), "evi_cosine_topk_gemm: a bf16 shadow goes with an f32 index and products = 1");
+    const int f16 = kind == kIdxF16;
+    const bool fp8 = kind >= kIdxFp8Widen;  // e4m3 rows: one selection precision (products = 3 runs two, see gemm_bf16x3.hip)
+    EVI_REQUIRE(!shadow || (single && kind == kIdxF32), "evi_cosine_topk_gemm: a bf16 shadow goes with an f32 index and products = 1");
+    EVI_REQUIRE(!fp8 || (!single && row_scale), "evi_cosine_topk_gemm_fp8: row_scale (the per-row dequantisation scale) is required");
     EVI_REQUIRE(Q >= 1 && N >= 1 && D >= 1, "evi_cosine_topk_gemm: need Q >= 1, N >= 1, D >= 1, got Q=%d N=%lld D=%d", Q,
                 (long long)N, D);
     EVI_REQUIRE(k >= 1, "evi_cosine_topk_gemm: k must be >= 1, got %d", k);
+    if (fp8 && (D % 64 != 0 || D > 1280))
+        return fail(EVI_ERR_UNSUPPORTED, "evi_cosine_topk_gemm_fp8: D must be a multiple of 64 up to 1280, got %d", D);
     if (D % (f16 ? 32 : 16) != 0)
         return fail(EVI_ERR_UNSUPPORTED, "evi_cosine_topk_gemm: D must be a multiple of %d, got %d", f16 ? 32 : 16, D);
     const int kk = gemm_topk_reserve(k, single);
@@ -1050,12 +1206,12 @@ static int cosine_topk_gemm_impl(const float* q, int Q, const void* idx, int f16
     float* exact = reinterpret_cast<float*>(base + L.exact);
     float* scores = reinterpret_cast<float*>(base + L.scores);
     // selection operand: the index itself, or its bf16 shadow (same arithmetic as products = 1, no conversion work)
-    const int a_kind = shadow ? 2 : f16;
+    const int a_kind = fp8 ? 3 : (shadow ? 2 : f16);
     const char* rows_base = static_cast<const char*>(shadow ? shadow : idx);
-    const size_t row_bytes = (size_t)D * (a_kind ? 2 : 4);
+    const size_t row_bytes = (size_t)D * (fp8 ? 1 : (a_kind ? 2 : 4));
     hipLaunchKernelGGL(k_gt_init, dim3((Q + 255) / 256), dim3(256), 0, st, tau, cnt, Q, status);
     EVI_LAUNCH_CHECK();
-    int rc = split_weight_bf16x3(q, Q, D, D, base + L.wsplit, st);  // the queries are the "weights": split once
+    int rc = gt_query_planes(kind, q, Q, D, base + L.wsplit, st);
     if (rc != EVI_OK) return rc;
     int64_t begin = 0, seg = N < kGemmFirstRows ? N : kGemmFirstRows;
     while (begin < N) {
@@ -1085,8 +1241,13 @@ static int cosine_topk_gemm_impl(const float* q, int Q, const void* idx, int f16
         int64_t next = begin * kGemmGrowth;
         seg = next < L.slab ? next : L.slab;
     }
-    hipLaunchKernelGGL(k_gt_gap, dim3(Q), dim3(64), 0, st, q, Q, D, cs, cnt, k, kk, single ? kApproxEps1 : kApproxEps, status);
-    if (f16)
+    hipLaunchKernelGGL(k_gt_gap, dim3(Q), dim3(64), 0, st, q, Q, D, cs, cnt, k, kk,
+                       fp8 ? kApproxEpsFp8 : (single ? kApproxEps1 : kApproxEps), kind == kIdxFp8Widen ? 1 : 0, status);
+    if (kind == kIdxFp8Mfma)
+        launch_rescore<Fp8MfmaRow>(kUntimed, st, q, D, idx, row_scale, ci, kGemmTopkCap, cnt, Q, kk, exact);
+    else if (kind == kIdxFp8Widen)
+        launch_rescore<Fp8WidenRow>(kUntimed, st, q, D, idx, row_scale, ci, kGemmTopkCap, cnt, Q, kk, exact);
+    else if (f16)
         launch_rescore<_Float16>(kUntimed, st, q, D, idx, row_scale, ci, kGemmTopkCap, cnt, Q, kk, exact);
     else
         launch_rescore<float>(kUntimed, st, q, D, idx, row_scale, ci, kGemmTopkCap, cnt, Q, kk, exact);
@@ -1100,15 +1261,44 @@ extern "C" int evi_cosine_topk_gemm(const float* q, int Q, const float* idx, int
                                     int k, int64_t row_id_base, int products, const void* shadow_bf16, float* out_score,
                                     int64_t* out_index, int32_t* status, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-    return cosine_topk_gemm_impl(q, Q, idx, 0, products, shadow_bf16, N, D, row_scale, k, row_id_base, out_score, out_index,
+    return cosine_topk_gemm_impl(q, Q, idx, kIdxF32, products, shadow_bf16, N, D, row_scale, k, row_id_base, out_score, out_index,
                                  status, workspace, workspace_bytes, stream);
 }
 
 extern "C" int evi_cosine_topk_gemm_f16(const float* q, int Q, const void* idx_f16, int64_t N, int D, const float* row_scale,
                                         int k, int64_t row_id_base, int products, float* out_score, int64_t* out_index,
                                         int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-    return cosine_topk_gemm_impl(q, Q, idx_f16, 1, products, nullptr, N, D, row_scale, k, row_id_base, out_score, out_index,
+    return cosine_topk_gemm_impl(q, Q, idx_f16, kIdxF16, products, nullptr, N, D, row_scale, k, row_id_base, out_score, out_index,
                                  status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int evi_cosine_topk_gemm_fp8(const float* q, int Q, const void* idx_fp8, int64_t N, int D, const float* row_scale,
+                                        int k, int64_t row_id_base, int native_mfma, float* out_score, int64_t* out_index,
+                                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    return cosine_topk_gemm_impl(q, Q, idx_fp8, native_mfma ? kIdxFp8Mfma : kIdxFp8Widen, 3, nullptr, N, D, row_scale, k,
+                                 row_id_base, out_score, out_index, status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int evi_cosine_topk_gemm_fp8_selection(const float* q, int Q, const void* idx_fp8, int64_t N, int D,
+                                                  const float* row_scale, int native_mfma, float* out_scores, void* workspace,
+                                                  size_t workspace_bytes, void* stream) {
+    EVI_REQUIRE(Q >= 1 && N >= 1, "evi_cosine_topk_gemm_fp8_selection: need Q >= 1 and N >= 1, got Q=%d N=%lld", Q, (long long)N);
+    if (D < 64 || D % 64 != 0 || D > 1280)
+        return fail(EVI_ERR_UNSUPPORTED, "evi_cosine_topk_gemm_fp8_selection: D must be a multiple of 64 up to 1280, got %d", D);
+    EVI_REQUIRE(q && idx_fp8 && row_scale && out_scores && workspace, "evi_cosine_topk_gemm_fp8_selection: null pointer");
+    if (workspace_bytes < gemm_bf16x3_workspace_bytes(Q, D))
+        return fail(EVI_ERR_NOMEM, "evi_cosine_topk_gemm_fp8_selection: workspace %zu B < %zu B", workspace_bytes,
+                    gemm_bf16x3_workspace_bytes(Q, D));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    int rc = gt_query_planes(native_mfma ? kIdxFp8Mfma : kIdxFp8Widen, q, Q, D, workspace, st);
+    if (rc != EVI_OK) return rc;
+    rc = launch_gemm_bf16_presplit(idx_fp8, 3, 0, N, D, D, workspace, Q, out_scores, Q, st);
+    if (rc != EVI_OK) return rc;
+    int64_t blocks = (N * Q + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_gt_scale_rows, dim3((unsigned)blocks), dim3(256), 0, st, out_scores, N, Q, row_scale);
+    EVI_LAUNCH_CHECK();
+    return EVI_OK;
 }
 
 // =====================================================================================================

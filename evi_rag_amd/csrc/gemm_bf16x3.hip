@@ -34,6 +34,16 @@ __device__ inline float act3(float v, int act) {
     return v;
 }
 
+// Two OCP e4m3 bytes of w (the low pair, or the high pair with `high`) -> two bf16 of the same values, exactly: the
+// hardware conversion to f32 is exact, and an e4m3 value has 3 mantissa bits, so the upper 16 bits of the f32 are the bf16.
+__device__ inline unsigned int e4m3x2_to_bf16x2(unsigned int w, bool high) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const f32x2 f = high ? __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+    // the two elements go through scalars: a bit cast applied to a vector ELEMENT expression reads element 0 for both
+    const float f0 = f[0], f1 = f[1];
+    return __builtin_amdgcn_perm(__float_as_uint(f1), __float_as_uint(f0), 0x07060302u);
+}
+
 // 16-byte slot of chunk c (0..3) of row r in a [rows][32 bf16] tile
 __device__ inline int slot3(int r, int c) { return r * 4 + (c ^ ((r >> 2) & 3)); }
 
@@ -72,6 +82,11 @@ __global__ void k_split_weight_long(const float* __restrict__ W, int N, int64_t 
 // AH = 1: A is stored as f16 (lda in halves) — an f16 value is exactly hi + lo in bf16, so nothing is lost.
 // AH = 2: A is a bf16 copy of the rows (the "shadow" of an f32 index, = its hi plane): staged without any
 //         conversion; only meaningful with P1 (there is no lo plane to multiply).
+// AH = 3: A is OCP e4m3 bytes, 1 B per element (lda in bytes), read from HBM as stored and widened to bf16 on the way into
+//         LDS.  Every e4m3 code is exactly a bf16 value (4 exponent and 3 mantissa bits inside bf16's 8 and 7), so the hi
+//         plane IS the operand and the lo plane is identically zero: it is neither staged nor multiplied, and the
+//         "three-product" form runs two (hi * Whi + hi * Wlo).  The widening carries no fixed factor (the scan's f16
+//         widening carries 1/256 because an e4m3 exponent does not fit f16's; bf16's range takes the value as it is).
 // P1 = 1: single product hi * hi (plain bf16 GEMM: relative error 2^-8 instead of 2^-16) — only for the candidate
 // selection of the many-query top-k, whose results are re-scored exactly; the lo planes are neither loaded,
 // staged nor multiplied.
@@ -99,9 +114,10 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
     }
     const int64_t w_ld = bt.count > 0 ? bt.w_ld : (int64_t)Kp;
     if (bt.count > 0) Kp = (K + XK - 1) / XK * XK;
-    constexpr bool kALo = P1 != 1;  // A lo plane staged and multiplied (three-product and f16x2 forms)
+    constexpr bool kALo = P1 != 1 && AH != 3;  // A lo plane staged and multiplied (three-product and f16x2 forms; e4m3 A has none)
     constexpr bool kWLo = P1 == 0;  // W lo plane (three-product form only)
     static_assert(P1 != 2 || AH == 0, "f16x2 takes f32 A");
+    static_assert(AH != 3 || P1 == 0, "e4m3 A: one selection precision (hi * Whi + hi * Wlo)");
     __shared__ uint4 sAhi[2][XM * 4], sWhi[2][XN * 4];                                     // 2 stages x 16 KiB each
     __shared__ uint4 sAlo[kALo ? 2 : 1][kALo ? XM * 4 : 1], sWlo[kWLo ? 2 : 1][kWLo ? XN * 4 : 1];  // lo planes where the form has them
     const int tid = threadIdx.x;
@@ -130,8 +146,9 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
 
     // Staging registers.  NS sets: a tile is loaded NS iterations before it is written to LDS.  One set when all three
     // products are multiplied (the register file is full); two with P1, whose k-tile takes a third of the MFMA time —
-    // with one set its loop ran at the latency of a global load per k-tile, not at the speed of its MFMAs.
-    constexpr int NS = P1 == 1 ? 2 : 1;
+    // with one set its loop ran at the latency of a global load per k-tile, not at the speed of its MFMAs.  Two also for
+    // e4m3 A: two products per k-tile, and its staging registers are a quarter of the f32 form's.
+    constexpr int NS = (P1 == 1 || AH == 3) ? 2 : 1;
     f32x4 ra[NS][4];
     u32x4 ra16[NS][2];  // AH != 0: two chunks of 8 halves per thread
     u32x4 rwh[NS][2], rwl[NS][2];
@@ -227,6 +244,30 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
         *reinterpret_cast<bf16x8*>(&sAhi[buf][slot3(r, c)]) = h;
         if (kALo) *reinterpret_cast<bf16x8*>(&sAlo[kALo ? buf : 0][kALo ? slot3(r, c) : 0]) = l;
     };
+    // e4m3 A: the k-tile is 256 rows x 32 B = 512 chunks of 16 B, one per thread (2 per row); 16 bytes widen to the two
+    // 16-byte bf16 chunks 2 c and 2 c + 1 of the row
+    auto load_a8 = [&](int set, int k0) {
+        const int r = tid >> 1, c = tid & 1;
+        const int k = k0 + c * 16;
+        const int64_t am = m0 + r;
+        const bool ok = am < M && k < K;
+        ra16[set][0] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(A) + (ok ? am * lda + k : 0));
+    };
+    auto store_a8 = [&](int set, int buf, int k0) {
+        const int r = tid >> 1, c = tid & 1;
+        const bool ok = m0 + r < M && k0 + c * 16 < K;
+        const u32x4 w = ok ? ra16[set][0] : zero16;
+        u32x4 lo8, hi8;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            lo8[2 * e] = e4m3x2_to_bf16x2(w[e], false);
+            lo8[2 * e + 1] = e4m3x2_to_bf16x2(w[e], true);
+            hi8[2 * e] = e4m3x2_to_bf16x2(w[2 + e], false);
+            hi8[2 * e + 1] = e4m3x2_to_bf16x2(w[2 + e], true);
+        }
+        *reinterpret_cast<u32x4*>(&sAhi[buf][slot3(r, 2 * c)]) = lo8;
+        *reinterpret_cast<u32x4*>(&sAhi[buf][slot3(r, 2 * c + 1)]) = hi8;
+    };
     auto store_w = [&](int set, int i, int buf, int k0) {
         const int s = tid + kXThreads * i;
         const int r = s >> 2, c = s & 3;
@@ -248,7 +289,9 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
     // written to the other stage piece by piece and the tile after it is fetched into the freed
     // registers; one barrier per k-tile.
     auto load_tile = [&](int set, int k0) {
-        if (AH) {
+        if (AH == 3) {
+            load_a8(set, k0);
+        } else if (AH) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) load_a16(set, i, k0);
         } else {
@@ -259,7 +302,9 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
         for (int i = 0; i < 2; ++i) load_w(set, i, k0);
     };
     load_tile(0, 0);
-    if (AH) {
+    if (AH == 3) {
+        store_a8(0, 0, 0);
+    } else if (AH) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) store_a16(0, i, 0, 0);
     } else {
@@ -320,13 +365,21 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
                     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, fah[g % RING]), wv, c, 0, 0, 0);
                     continue;
                 }
-                if (!P1) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal[g % RING], fbh[ks][j], c, 0, 0, 0);
+                if (kALo) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal[g % RING], fbh[ks][j], c, 0, 0, 0);
                 if (!P1) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah[g % RING], fbl[ks][j], c, 0, 0, 0);
                 c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fah[g % RING], fbh[ks][j], c, 0, 0, 0);
             }
             // one staging piece in the shadow of this group's MFMAs (pieces 0-3: A, 4-5: W).  Past the last
             // tile the pieces move zeros into a stage nobody reads: cheaper than a branch in this loop.
-            if (AH) {
+            if (AH == 3) {
+                if (g == 0) {
+                    store_a8(set, cur ^ 1, k0 + XK);
+                    load_a8(set, k0 + (1 + NS) * XK);
+                } else if (g >= 4 && g < 6) {
+                    store_w(set, g - 4, cur ^ 1, k0 + XK);
+                    load_w(set, g - 4, k0 + (1 + NS) * XK);
+                }
+            } else if (AH) {
                 if (g < 2) {
                     store_a16(set, g, cur ^ 1, k0 + XK);
                     load_a16(set, g, k0 + (1 + NS) * XK);
@@ -411,6 +464,13 @@ size_t gemm_bf16x3_workspace_bytes(int N, int K) {
     return align_up((size_t)N * Kp * 2, 256) * 2;
 }
 
+// where the two planes of W [N, K] sit in `wsplit` and their row stride, for a caller that writes them itself
+void bf16x3_planes(void* wsplit, int N, int K, __bf16** hi, __bf16** lo, int* Kp) {
+    *Kp = (K + XK - 1) / XK * XK;
+    *hi = static_cast<__bf16*>(wsplit);
+    *lo = reinterpret_cast<__bf16*>(static_cast<char*>(wsplit) + align_up((size_t)N * *Kp * 2, 256));
+}
+
 // wsplit: gemm_bf16x3_workspace_bytes(N, K) bytes of scratch for the split weight planes.
 int split_weight_bf16x3(const float* W, int N, int K, int64_t ldw, void* wsplit, hipStream_t st) {
     const int Kp = (K + XK - 1) / XK * XK;
@@ -434,7 +494,8 @@ int launch_gemm_bf16_presplit(const void* A, int a_f16, int single, int64_t M, i
 #define EVI_LAUNCH_PS(AHV, P1V)                                                                                          \
     hipLaunchKernelGGL((k_gemm_nt_bf16x3<0, AHV, P1V>), grid, dim3(kXThreads), 0, st, static_cast<const float*>(A), M, K, lda, \
                        hi, lo, N, Kp, static_cast<const float*>(nullptr), C, ldc, flt, GemmBatch{})
-    if (a_f16 == 2) EVI_LAUNCH_PS(2, 1);
+    if (a_f16 == 3) EVI_LAUNCH_PS(3, 0);
+    else if (a_f16 == 2) EVI_LAUNCH_PS(2, 1);
     else if (a_f16 && single) EVI_LAUNCH_PS(1, 1);
     else if (a_f16) EVI_LAUNCH_PS(1, 0);
     else if (single) EVI_LAUNCH_PS(0, 1);
@@ -456,7 +517,8 @@ int launch_gemm_bf16x3_filter(const void* A, int a_f16, int single, int64_t M, i
 #define EVI_LAUNCH_FL(AHV, P1V)                                                                                          \
     hipLaunchKernelGGL((k_gemm_nt_bf16x3<3, AHV, P1V>), grid, dim3(kXThreads), 0, st, static_cast<const float*>(A), M, K, lda, \
                        hi, lo, N, Kp, static_cast<const float*>(nullptr), static_cast<float*>(nullptr), (int64_t)0, flt, GemmBatch{})
-    if (a_f16 == 2) EVI_LAUNCH_FL(2, 1);
+    if (a_f16 == 3) EVI_LAUNCH_FL(3, 0);
+    else if (a_f16 == 2) EVI_LAUNCH_FL(2, 1);
     else if (a_f16 && single) EVI_LAUNCH_FL(1, 1);
     else if (a_f16) EVI_LAUNCH_FL(1, 0);
     else if (single) EVI_LAUNCH_FL(0, 1);

@@ -194,15 +194,21 @@ def cosine_topk(
           * an f32 index whose f16 shadow is resident (built by `index_shadow_f16(index)`, which attaches it to the
             tensor): the two-stage scan — half the HBM bytes per batch; a batch whose exactness proof fails is re-done
             by the gated f32 scan ON THE DEVICE, nothing is read back (2.36 vs 4.57 ms per batch at 2^23 x 768);
-          * else the scan.
+          * else the scan.  An e4m3 (uint8) index stays on the scan at every Q: the many-query
+            pass exists for it (method "gemm") but has not been measured against the 16-pass scan at the config-5 shard
+            shape yet, and "auto" takes no path on an unmeasured promise.
       "scan": 32 queries per pass over the index, never synchronises.
-      "gemm": force the GEMM-shaped pass (see cosine_topk_gemm).
+      "gemm": force the GEMM-shaped pass (see cosine_topk_gemm); over an e4m3 index it reproduces the scan variant
+          `fp8_mfma` names.
     fp8_mfma (e4m3 index only; default None = True): feed the index bytes to the native fp8 matrix instruction with the
     query as two e4m3 pieces (evi_cosine_topk_fp8_mfma) — no conversion work on the stream (5.86 vs 5.43 TB/s); scores
     carry 16 significant query bits, ~20x inside the index's own quantisation noise (overlap@500 with the widening
     variant 0.999).  False: widen the index bytes to f16 in registers and keep the f32 query exact."""
     if method not in ("scan", "gemm", "auto"):
         raise ValueError(f"method must be 'scan', 'gemm' or 'auto', got {method!r}")
+    if method == "gemm" and index.dtype == torch.uint8 and queries.dim() == 2 and index.dim() == 2:
+        cosine_topk.last_method = "gemm"
+        return cosine_topk_gemm(queries, index, k, row_scale=row_scale, row_id_base=row_id_base, out=out, fp8_mfma=fp8_mfma)
     if method != "scan" and index.dtype in (torch.float32, torch.float16) and queries.dim() == 2 and index.dim() == 2:
         eligible = index.size(1) % (32 if index.dtype == torch.float16 else 16) == 0 and _reserve_fits(k) and index.size(0) >= 1 and queries.size(0) >= 1
         if method == "gemm" or (eligible and queries.size(0) >= 96):
@@ -282,9 +288,17 @@ def resident_shadow_f16(index: torch.Tensor) -> Optional[torch.Tensor]:
     return shadow
 
 
+# Selection error bound of the many-query pass over an e4m3 index, per unit of |q| |stored row| (kApproxEpsFp8Unit in
+# cosine_topk.hip, derived there), and the stored-row norm its proof is stated for: a unit row rounded to e4m3 (4
+# significant bits) is stored with norm <= 1 + 2^-4.
+GEMM_FP8_EPS_UNIT = 4.8e-4
+GEMM_FP8_ROW_NORM_MAX = 1.0 + 2.0 ** -4
+
+
 def rows_are_unit_norm(index: torch.Tensor, row_scale: Optional[torch.Tensor] = None) -> bool:
-    """True when every (scaled) row of `index` has norm <= 1 + 1e-4 (1 + 1e-3 for an f16-stored index) — what the exactness proofs of the GEMM-shaped and
-    two-stage paths assume (their error bounds are kEps * |q| * |x| with |x| <= 1).  One pass over the index and one
+    """True when every (scaled) row of `index` has norm <= 1 + 1e-4 (1 + 1e-3 for an f16-stored index; 1 + 2^-4 for an
+    e4m3 index, uint8 + row_scale, whose stored rows are codes x scale) — what the exactness proofs of the GEMM-shaped and
+    two-stage paths assume (their error bounds are kEps * |q| * |x| with |x| <= 1, <= 1 + 2^-4 for e4m3).  One pass over the index and one
     read-back, cached ON the index tensor per (version, row_scale object + version): in-place edits are seen, and the
     verdict cannot outlive the tensor (a new tensor at a recycled address starts unverified)."""
     import weakref
@@ -305,12 +319,15 @@ def rows_are_unit_norm(index: torch.Tensor, row_scale: Optional[torch.Tensor] = 
             x = index if index.dtype == torch.float32 else None
             if x is not None:
                 norms = row_norms(x)
-            else:  # f16 storage: chunked, in f32
-                norms = torch.cat([index[i: i + (1 << 20)].float().norm(dim=1) for i in range(0, index.size(0), 1 << 20)])
+            else:  # f16 / e4m3 storage: chunked, in f32
+                def wide(part):
+                    return (part.view(torch.float8_e4m3fn) if part.dtype == torch.uint8 else part).float()
+                norms = torch.cat([wide(index[i: i + (1 << 20)]).norm(dim=1) for i in range(0, index.size(0), 1 << 20)])
             if row_scale is not None:
                 norms = norms * row_scale.view(-1).abs()
-            # f16 storage: rounding a unit row element by element moves its norm by up to 2^-11 (5e-4)
-            hit = bool((norms.max() <= 1.0 + (1e-4 if index.dtype == torch.float32 else 1e-3)).item())
+            # f16 storage: rounding a unit row element by element moves its norm by up to 2^-11 (5e-4); e4m3: by up to 2^-4
+            limit = {torch.float32: 1.0 + 1e-4, torch.uint8: GEMM_FP8_ROW_NORM_MAX}.get(index.dtype, 1.0 + 1e-3)
+            hit = bool((norms.max() <= limit).item())  # a NaN norm (e4m3 NaN code) fails: the scan takes such an index
         cache["unit_rows"] = (index._version, index.data_ptr(), None if row_scale is None else weakref.ref(row_scale),
                               None if row_scale is None else row_scale._version, hit)
     return hit
@@ -320,20 +337,27 @@ def cosine_topk_gemm(queries: torch.Tensor, index: torch.Tensor, k: int, *, row_
                      row_id_base: int = 0, fallback: bool = True,
                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                      products: Optional[int] = None, shadow: Optional[torch.Tensor] = None,
-                     check_norms: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+                     check_norms: bool = True, fp8_mfma: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """cosine_topk for many queries at once (see evi_cosine_topk_gemm): one split-bf16 GEMM pass over the index
     selects candidates, the scan's arithmetic re-scores them; the result equals cosine_topk bit for bit.  Reads the
     proof flag back (one synchronisation); when the proof fails (heavy score ties, adversarial row order) the scan
     runs instead (fallback=True) or RuntimeError is raised.  products: 3 (split-bf16 selection), 1 (plain bf16 selection:
-    three times fewer MFMAs, proof fails earlier) or None = try 1 when k <= 1024, then 3, then the scan."""
+    three times fewer MFMAs, proof fails earlier) or None = try 1 when k <= 1024, then 3, then the scan.
+    An e4m3 index (uint8 + row_scale from quantize_rows_fp8; D a multiple of 64 up to 1280) takes
+    evi_cosine_topk_gemm_fp8: the stored bytes are streamed once and widened to bf16 exactly inside the GEMM, two bf16
+    products.  fp8_mfma has the meaning and default (None = True) it has in cosine_topk: the result equals, bit for
+    bit, the scan of THAT variant, and the scan fallback runs that variant.  There is one selection precision, so
+    `products` must stay None, and no `shadow`.  The norm check allows stored rows (codes x scale) up to 1 + 2^-4."""
     if products not in (None, 1, 3):
         raise ValueError(f"products must be None, 1 or 3, got {products}")
+    if index.dtype == torch.uint8:
+        return _cosine_topk_gemm_fp8(queries, index, k, row_scale, row_id_base, fallback, out, products, shadow, check_norms, fp8_mfma)
+    if fp8_mfma:
+        raise ValueError("fp8_mfma goes with an e4m3 (uint8) index")
     if shadow is not None:
         if index.dtype != torch.float32 or shadow.dtype != torch.bfloat16 or shadow.shape != index.shape or not shadow.is_contiguous():
             raise ValueError("shadow must be the contiguous bfloat16 copy of an f32 index (index_shadow_bf16)")
     dev = _require_gpu(queries, index, row_scale)
-    if index.dtype == torch.uint8:
-        raise ValueError(f"index must be float32 or float16, got {index.dtype}")
     q, x, row_scale = _topk_operands(queries, index, row_scale)  # f16 storage: evi_cosine_topk_gemm_f16
     Q, D = q.shape
     N = x.shape[0]
@@ -378,6 +402,73 @@ def cosine_topk_gemm(queries: torch.Tensor, index: torch.Tensor, k: int, *, row_
 
 
 cosine_topk_gemm.last_products = None
+
+
+def _cosine_topk_gemm_fp8(queries, index, k, row_scale, row_id_base, fallback, out, products, shadow, check_norms, fp8_mfma):
+    """cosine_topk_gemm over an e4m3 index (see there)."""
+    if products is not None:
+        raise ValueError("an e4m3 index has one selection precision: products must be None")
+    if shadow is not None:
+        raise ValueError("shadow goes with an f32 index, not an e4m3 one")
+    if row_scale is None:
+        raise ValueError("an fp8 index needs row_scale (the per-row scale returned by quantize_rows_fp8)")
+    dev = _require_gpu(queries, index, row_scale)
+    scale_given = row_scale  # the caller's tensor object: what the cached norm verdict is keyed on
+    q, x, row_scale = _topk_operands(queries, index, row_scale)
+    Q, D = q.shape
+    N = x.shape[0]
+    native = True if fp8_mfma is None else bool(fp8_mfma)
+
+    def scan():
+        return cosine_topk(q, x, k, row_scale=row_scale, row_id_base=row_id_base, out=out, method="scan", fp8_mfma=native)
+
+    if Q == 0 or N == 0:
+        return scan()
+    if check_norms and not rows_are_unit_norm(x, scale_given):
+        if not fallback:
+            raise ValueError("cosine_topk_gemm needs rows of norm <= 1 (normalize_embeddings before quantize_rows_fp8; stored "
+                             "e4m3 rows may reach 1 + 2^-4): its exactness proof assumes them")
+        cosine_topk_gemm.last_products = 0
+        return scan()
+    lib = _lib.load()
+    ws = _workspace(dev, "cosine_topk_gemm", int(lib.evi_cosine_topk_gemm_workspace_bytes(Q, N, D, int(k))))
+    out_score, out_index = _topk_out(out, Q, k, dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.evi_cosine_topk_gemm_fp8(_ptr(q), Q, _ptr(x), N, D, _ptr(row_scale), int(k), int(row_id_base), int(native),
+                                            _ptr(out_score), _ptr(out_index), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            _stream(dev)))
+    st = int(status.item())
+    cosine_topk_gemm.last_status = st  # 0 proven; 1 gap test failed; 2 a candidate list overflowed (introspection / bench)
+    if st != 0:
+        cosine_topk_gemm.last_products = 0  # the scan produced the result
+        if not fallback:
+            raise RuntimeError(f"evi_cosine_topk_gemm_fp8 could not prove exactness (status {st}): run cosine_topk")
+        return scan()
+    cosine_topk_gemm.last_products = 3  # the split-bf16 selection (two products run: the index has no lo plane)
+    return out_score, out_index
+
+
+cosine_topk_gemm.last_status = None
+
+
+def cosine_topk_gemm_fp8_selection_scores(queries: torch.Tensor, index: torch.Tensor, row_scale: torch.Tensor, *,
+                                          fp8_mfma: bool = True) -> torch.Tensor:
+    """The selection scores [N, Q] that cosine_topk_gemm forms over an e4m3 index (row_scale applied) — for checking
+    its error bound GEMM_FP8_EPS_UNIT * |q| * |row| against the scan of the same variant; not a search entry point."""
+    dev = _require_gpu(queries, index, row_scale)
+    if index.dtype != torch.uint8:
+        raise ValueError("index must be e4m3 bytes (uint8)")
+    q, x, row_scale = _topk_operands(queries, index, row_scale)
+    Q, D = q.shape
+    N = x.shape[0]
+    out = torch.empty((N, Q), dtype=torch.float32, device=dev)
+    if Q == 0 or N == 0:
+        return out
+    lib = _lib.load()
+    ws = _workspace(dev, "cosine_topk_gemm", int(lib.evi_gemm_nt_bf16x3_workspace_bytes(Q, D)))
+    _lib.check(lib.evi_cosine_topk_gemm_fp8_selection(_ptr(q), Q, _ptr(x), N, D, _ptr(row_scale), int(bool(fp8_mfma)), _ptr(out),
+                                                      ws.data_ptr(), ws.numel(), _stream(dev)))
+    return out
 
 
 def index_shadow_f16(index: torch.Tensor, *, check_norms: bool = True, attach: bool = True) -> torch.Tensor:

@@ -167,6 +167,25 @@ int evi_cosine_topk_gemm(const float* q, int Q, const float* idx, int64_t N, int
 int evi_cosine_topk_gemm_f16(const float* q, int Q, const void* idx_f16, int64_t N, int D, const float* row_scale,
                              int k, int64_t row_id_base, int products, float* out_score, int64_t* out_index,
                              int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The same over an e4m3 index with its per-row scale (row_scale required; D a multiple of 64 up to 1280, else
+ * EVI_ERR_UNSUPPORTED): bit-identical to evi_cosine_topk_fp8 (native_mfma = 0) or evi_cosine_topk_fp8_mfma
+ * (native_mfma != 0), one pass over the index instead of ceil(Q / 32).  The slab is read as the stored bytes and widened
+ * to bf16 - exactly: every e4m3 code is a bf16 value - on the way into LDS; no bf16 or f16 copy of the index exists in
+ * HBM.  The index side of the selection product carries no rounding, so two bf16 products (query hi, query lo) do what
+ * three do for f32.  The query planes are the bf16 hi / lo split of the f32 query for the widening variant and, for the
+ * native variant, the same two dequantised e4m3 pieces the scan multiplies (selection and scan then differ by
+ * accumulation order only).  Selection error <= 4.8e-4 |q| |row| for stored rows (codes x scale) of norm <= 1 + 2^-4,
+ * which the CALLER guarantees; reserve max(256, k/2), k <= 1365; workspace: evi_cosine_topk_gemm_workspace_bytes.
+ * *status as for evi_cosine_topk_gemm; the widening variant also refuses (status 1) a query with |q| outside [1/4, 4]. */
+int evi_cosine_topk_gemm_fp8(const float* q, int Q, const void* idx_fp8, int64_t N, int D, const float* row_scale,
+                             int k, int64_t row_id_base, int native_mfma, float* out_score, int64_t* out_index,
+                             int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The selection scores of evi_cosine_topk_gemm_fp8 themselves, out_scores [N, Q] (row-major, row_scale applied): what
+ * the candidate lists are filled from.  For verifying the error bound against the scan; workspace >=
+ * evi_gemm_nt_bf16x3_workspace_bytes(Q, D). */
+int evi_cosine_topk_gemm_fp8_selection(const float* q, int Q, const void* idx_fp8, int64_t N, int D,
+                                       const float* row_scale, int native_mfma, float* out_scores, void* workspace,
+                                       size_t workspace_bytes, void* stream);
 
 /* Two-stage exact scan: the result of evi_cosine_topk (ids and scores bit-identical) at half the HBM bytes per
  * batch, for an f32 index of rows with norm <= 1 (evi_row_normalize output; no row_scale) that is kept together
