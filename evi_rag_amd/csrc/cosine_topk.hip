@@ -8,8 +8,10 @@
 //   The index [N, D] f32 lives in HBM and is streamed exactly once per batch of <= 32 queries.
 //   Each wave owns 16 index rows at a time and loads them straight into MFMA B-fragments
 //   (lane (n = l&15, g = l>>4) reads 16 B of row n at column 16 j + 4 g): no LDS round trip for
-//   the stream, which no other wave reuses.  The <= 32 queries are pre-fragmented once into the
-//   A-operand order and parked in LDS for the whole launch (D * 128 B: 96 KiB at D = 768).
+//   the stream, which no other wave reuses.  The loads run one group ahead of the MFMAs, across
+//   tile boundaries, and nothing on the common path waits for more than the group it multiplies.
+//   The <= 32 queries are pre-fragmented once into the A-operand order and parked in LDS for the
+//   whole launch (D * 128 B: 96 KiB at D = 768).
 //   v_mfma_f32_16x16x4_f32 computes the [32 queries x 16 rows] block as an exact f32 FMA chain
 //   in a fixed order of d, so a row's score never depends on where the row sits.
 //
@@ -238,8 +240,10 @@ __device__ inline uint32_t fp8x2_to_f16x2_scaled(uint32_t w, uint32_t sel) {
 
 
 // One pass over rows [seg_begin, seg_end) of the shard.
-//   NQB: query blocks of 16 (1 or 2).  U: float4 loads in flight per lane per prefetch group
-//   (U divides D/16).  kScanThreads per workgroup (one workgroup per CU: LDS holds the queries).
+//   NQB: query blocks of 16 (1 or 2).  U: float4 loads per lane per load group (U divides D/16).  A wave keeps
+//   kScanSets register sets of U float4: while one group is multiplied, kScanSets - 1 later ones are in flight.
+//   kScanThreads per workgroup (one workgroup per CU: LDS holds the queries).
+//   SCALE: scores are multiplied by row_scale[row] (a compile-time variant: its load is part of the counted stream).
 // Appends are staged per workgroup in LDS (capq entries per query) and flushed once at the end
 // with one global atomic per query, so the per-query cursors see ~256 atomics per launch instead
 // of one per candidate; entries that do not fit go straight to the global list.
@@ -247,9 +251,10 @@ __device__ inline uint32_t fp8x2_to_f16x2_scaled(uint32_t w, uint32_t sel) {
 //   multiplied on v_mfma_f32_16x16x32_f16 with f32 accumulation.
 //   (F16 == 2: the index is OCP e4m3 with a per-row scale; bytes are widened to f16 in registers.)
 constexpr int kScanThreads = 1024;
-constexpr int kScanMaxU = 4;  // most loads in flight per lane per group
+constexpr int kScanMaxU = 4;  // most loads per lane per group
+constexpr int kScanSets = 2;  // register sets of a wave's stream: one group (4 KiB per wave at U = 4) ahead of the MFMAs
 
-template <int NQB, int U, int F16>
+template <int NQB, int U, int F16, bool SCALE>
 __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
     const float* __restrict__ qfrag, const void* __restrict__ idx, int64_t seg_begin,
     int64_t seg_end, int D, int Q, const float* __restrict__ row_scale,
@@ -259,6 +264,7 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
     extern __shared__ float4 lds_q[];  // [(D/16)*4][NQB*16] float4, then the append staging area
     constexpr int NQ = NQB * 16;
     constexpr int WAVES = kScanThreads / 64;
+    constexpr int NS = kScanSets;
     const int tid = threadIdx.x;
     const int chunks = F16 >= 2 ? D / 64 : (F16 ? D / 32 : D / 16);  // 64-byte pieces of a row
     const int qslots = F16 == 3 ? (D / 8) * NQ  // native fp8: two 1-byte pieces per element, D * NQ * 2 bytes
@@ -273,7 +279,7 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
     }
     __syncthreads();
 
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // tile and group counters stay scalar
     const int n = lane & 15, g = lane >> 4;
     float tq[NQB][4];
 #pragma unroll
@@ -281,7 +287,7 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int qi = b * 16 + 4 * g + r;
-            tq[b][r] = (dense || qi >= Q) ? -INFINITY : tau[qi];
+            tq[b][r] = qi >= Q ? INFINITY : (dense ? -INFINITY : tau[qi]);
         }
 
     float qs1[NQB][4], qs2[NQB][4];  // native fp8: the two piece scales of this lane's queries
@@ -297,27 +303,32 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
             }
     }
     const int64_t seg_rows = seg_end - seg_begin;
-    const int64_t tiles = (seg_rows + 15) / 16;
+    const int tiles = (int)((seg_rows + 15) / 16);  // a shard holds < 2^31 rows: tile indices are 32-bit scalars
     const int groups = chunks / U;
     const float4* lq = lds_q + g * NQ + n;  // + (j*4)*NQ + b*16
 
-    // The wave's work is ONE stream of load groups (U float4 per lane each) that runs across tile
-    // boundaries: while group i is multiplied, group i+1 — possibly the first group of the wave's
-    // next tile — is already in flight, in a second register set (ping-pong, no copies).  Every
-    // iteration therefore has the same number of loads outstanding, so the compiler's counted
-    // vmcnt waits release exactly the group that is needed and never drain the prefetch.
-    const int64_t stride = (int64_t)gridDim.x * WAVES;
+    // The wave's work is ONE stream of load groups (U float4 per lane each) that runs across tile boundaries, walked by ONE
+    // loop: a step loads the next group of the stream - possibly the first group of the wave's next tile - into one
+    // register set, multiplies the group that is in the other, and runs the tile's epilogue when that was the tile's last
+    // group.  Two steps with the sets' roles swapped make the loop body, whatever the parity of the group count, so the
+    // group in flight across a tile boundary is a loop-carried value of that loop: it is never copied, and every counted
+    // vmcnt wait leaves the U newest loads outstanding.  row_scale[row] of a tile is loaded right after the previous
+    // tile's epilogue (behind that tile's already issued first group, ahead of every later one), so the epilogue's wait for
+    // it leaves at least the newest group outstanding, and the eight threshold tests of a filtered tile end
+    // in one ballot: a tile without a candidate (nearly all of them) runs no per-slot code and waits on nothing.
+    const int stride = (int)gridDim.x * WAVES;
     const int64_t row_bytes = (int64_t)D * (F16 >= 2 ? 1 : (F16 ? 2 : 4));
-    auto tile_ptr = [&](int64_t t) -> const f32x4* {
-        const int64_t r = seg_begin + t * 16 + n;
+    auto tile_ptr = [&](int t) -> const f32x4* {
+        const int64_t r = seg_begin + (int64_t)t * 16 + n;
         const int64_t rc = r < seg_end ? r : seg_end - 1;
         return reinterpret_cast<const f32x4*>(static_cast<const char*>(idx) + rc * row_bytes) + g;
     };
-    auto load_group = [&](f32x4 (&x)[U], const f32x4* xp, int gi) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) x[u] = xp[(gi * U + u) * 4];
-    };
     f32x4 acc[NQB], acc_lo[NQB];
+    float4 an[NQB];  // f32 rows: the A fragments of the chunk that is multiplied next
+    if (F16 == 0) {
+#pragma unroll
+        for (int b = 0; b < NQB; ++b) an[b] = lq[b * 16];
+    }
     auto mul_group = [&](const f32x4 (&x)[U], int gi) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -369,78 +380,134 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
                 }
                 continue;
             }
+            // the A fragments of chunk j were read from LDS one chunk ahead (an), the next chunk's are read here, ahead of
+            // this chunk's MFMAs; past the tile's last chunk comes chunk 0 of the next tile
             float4 a[NQB];
 #pragma unroll
-            for (int b = 0; b < NQB; ++b) a[b] = lq[(j * 4) * NQ + b * 16];
+            for (int b = 0; b < NQB; ++b) a[b] = an[b];
+            const int jn = j + 1 < chunks ? j + 1 : 0;
 #pragma unroll
-            for (int b = 0; b < NQB; ++b) {
-                const float ab[4] = {a[b].x, a[b].y, a[b].z, a[b].w};
+            for (int b = 0; b < NQB; ++b) an[b] = lq[(jn * 4) * NQ + b * 16];
+            __builtin_amdgcn_sched_barrier(0);  // or the reads sink back to just above their first use
+            // e outer, query block inner: the two accumulators' chains alternate, so no MFMA waits for the one before
+            // it; each accumulator still sees j ascending and, within j, e ascending
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(ab[e], x[u][e], acc[b], 0, 0, 0);
-            }
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int b = 0; b < NQB; ++b) {
+                    const float ab = e == 0 ? a[b].x : (e == 1 ? a[b].y : (e == 2 ? a[b].z : a[b].w));
+                    acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(ab, x[u][e], acc[b], 0, 0, 0);
+                }
         }
     };
 
-    int64_t t = (int64_t)blockIdx.x * WAVES + wave;
-    const f32x4* xp = tile_ptr(t < tiles ? t : 0);
-    f32x4 xa[U], xb[U];
-    if (t < tiles) load_group(xa, xp, 0);
-    for (; t < tiles; t += stride) {
-        const int64_t tn = t + stride;
-        const f32x4* xpn = tile_ptr(tn < tiles ? tn : t);  // past the end: a harmless re-read
-        const int64_t row = seg_begin + t * 16 + n;
+    // the tile's scores against the thresholds; `scale` is row_scale[row] (SCALE only)
+    auto epilogue = [&](int64_t row, float scale) {
+        float s[NQB][4];
+#pragma unroll
+        for (int b = 0; b < NQB; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float dot = F16 == 3 ? fmaf(acc_lo[b][r], qs2[b][r], acc[b][r] * qs1[b][r])
+                            : (F16 ? fmaf(acc_lo[b][r], 1.0f / kLoScale, acc[b][r]) : acc[b][r]);
+                if (F16 == 2) dot *= 256.0f;  // the widened bytes carry value / 256
+                s[b][r] = SCALE ? dot * scale : dot;
+            }
+        if (dense) {  // the first segment: every score is written, nothing is tested
+            if (row < seg_end) {
+                const int64_t pos = row - seg_begin;
+#pragma unroll
+                for (int b = 0; b < NQB; ++b)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int qi = b * 16 + 4 * g + r;
+                        // the id of a dense entry is its position (seg_begin == 0): not stored
+                        if (qi < Q) cand_score[qi * cap + pos] = s[b][r];
+                    }
+            }
+            return;
+        }
+        bool any = false;  // tq is +inf for a query slot past Q; !(s < tq) also lets a NaN score through
+#pragma unroll
+        for (int b = 0; b < NQB; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) any |= !(s[b][r] < tq[b][r]);
+        any &= row < seg_end;
+        if (__ballot(any) == 0) return;
+        if (!any) return;  // among them the lanes of a ragged last tile whose row lies past the segment
+        // rare from here on.  The slot addresses are derived from an opaque copy of g, so that the compiler computes them
+        // here and does not keep sixteen address registers alive through the stream.
+        int gq = g;
+        asm volatile("" : "+v"(gq));
+#pragma unroll
+        for (int b = 0; b < NQB; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int qi = b * 16 + 4 * gq + r;
+                if (qi >= Q || !(s[b][r] >= tq[b][r] || s[b][r] != s[b][r])) continue;
+                const int p = atomicAdd(&lds_cnt[qi], 1);
+                if (p < capq) {
+                    lds_sc[qi * capq + p] = s[b][r];
+                    lds_id[qi * capq + p] = (int32_t)row;
+                } else {
+                    const int32_t pos = atomicAdd(&cand_cnt[qi * kCntStride], 1);
+                    cand_score[qi * cap + pos] = s[b][r];
+                    cand_id[qi * cap + pos] = (int32_t)row;
+                }
+            }
+    };
+
+    const int t0 = (int)blockIdx.x * WAVES + wave;
+    if (t0 < tiles) {
+        // load cursor: group gl of tile tl comes next, from lp; multiply cursor: group gm of tile tm
+        int tl = t0, tm = t0;
+        int gl = 0, gm = 0;
+        const f32x4* lp = tile_ptr(tl);
+        float scale = 1.0f;
+        auto load_scale = [&]() {
+            if (SCALE) {
+                const int64_t r = seg_begin + (int64_t)tm * 16 + n;
+                scale = row_scale[r < seg_end ? r : seg_end - 1];
+            }
+        };
+        auto load_next = [&](f32x4 (&x)[U]) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) x[u] = lp[u * 4];
+            if (++gl < groups) {
+                lp += U * 4;
+            } else {  // on to the wave's next tile; past its last one: a harmless re-read of this tile's first group
+                gl = 0;
+                const int tn = tl + stride;
+                tl = tn < tiles ? tn : tl;
+                lp = tile_ptr(tl);
+            }
+        };
+        // one step of the stream.  The loop leaves only at its bottom, so a wave may run up to NS - 1 steps past its last
+        // tile: they multiply a re-read group and end in no epilogue.  (With an exit after every step the compiler funnels
+        // all of them through one latch block, and its wait counts then allow for paths on which a step was skipped.)
+        auto step = [&](const f32x4 (&cur)[U], f32x4 (&nxt)[U]) {
+            load_next(nxt);
+            __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ahead of the MFMAs it overlaps
+            mul_group(cur, gm);
+            __builtin_amdgcn_sched_barrier(0);
+            if (++gm < groups) return;
+            if (tm < tiles) epilogue(seg_begin + (int64_t)tm * 16 + n, scale);
+            gm = 0;
+            tm += stride;
+#pragma unroll
+            for (int b = 0; b < NQB; ++b) acc[b] = acc_lo[b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            load_scale();
+        };
+        f32x4 x[NS][U];
 #pragma unroll
         for (int b = 0; b < NQB; ++b) acc[b] = acc_lo[b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if ((groups & 1) == 0) {
-            for (int gi = 0; gi < groups; gi += 2) {
-                load_group(xb, xp, gi + 1);
-                __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ahead of the MFMAs it overlaps
-                mul_group(xa, gi);
-                __builtin_amdgcn_sched_barrier(0);
-                if (gi + 2 < groups) load_group(xa, xp, gi + 2); else load_group(xa, xpn, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                mul_group(xb, gi + 1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {  // odd group count: same stream, with a register copy per group
-            for (int gi = 0; gi < groups; ++gi) {
-                if (gi + 1 < groups) load_group(xb, xp, gi + 1); else load_group(xb, xpn, 0);
-                mul_group(xa, gi);
+        load_scale();
 #pragma unroll
-                for (int u = 0; u < U; ++u) xa[u] = xb[u];
-            }
-        }
-        xp = xpn;
-
-        if (row < seg_end) {
-            const float scale = row_scale ? row_scale[row] : 1.0f;
+        for (int s = 0; s < NS - 1; ++s) load_next(x[s]);
+        do {
 #pragma unroll
-            for (int b = 0; b < NQB; ++b)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int qi = b * 16 + 4 * g + r;
-                    if (qi >= Q) continue;
-                    float dot = F16 == 3 ? fmaf(acc_lo[b][r], qs2[b][r], acc[b][r] * qs1[b][r])
-                                : (F16 ? fmaf(acc_lo[b][r], 1.0f / kLoScale, acc[b][r]) : acc[b][r]);
-                    if (F16 == 2) dot *= 256.0f;  // the widened bytes carry value / 256
-                    const float s = row_scale ? dot * scale : dot;
-                    if (dense) {
-                        const int64_t pos = row - seg_begin;
-                        cand_score[qi * cap + pos] = s;  // the id of a dense entry is its position (seg_begin == 0): not stored
-                    } else if (s >= tq[b][r] || s != s) {
-                        const int p = atomicAdd(&lds_cnt[qi], 1);
-                        if (p < capq) {
-                            lds_sc[qi * capq + p] = s;
-                            lds_id[qi * capq + p] = (int32_t)row;
-                        } else {
-                            const int32_t pos = atomicAdd(&cand_cnt[qi * kCntStride], 1);
-                            cand_score[qi * cap + pos] = s;
-                            cand_id[qi * cap + pos] = (int32_t)row;
-                        }
-                    }
-                }
-        }
+            for (int s = 0; s < NS; ++s) step(x[s], x[(s + NS - 1) % NS]);
+        } while (tm < tiles);
     }
 
     if (!dense && capq > 0) {
@@ -544,27 +611,40 @@ struct ScoreArgs {
     const int32_t* gate;
 };
 
-template <int NQB, int U, int KIND>
+template <int NQB, int U, int KIND, bool SCALE>
 static int launch_score(const ScoreArgs& a) {
     static thread_local bool attr_set = false;
     if (!attr_set) {
-        EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cosine_score<NQB, U, KIND>),
+        EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cosine_score<NQB, U, KIND, SCALE>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
     // gated launches (the fallback of a proof-carrying path) stay out of the timing accounts
-    launch_timed(a.gate ? kUntimed : kTimeCosineScore, k_cosine_score<NQB, U, KIND>, dim3(a.grid), dim3(kScanThreads), a.lds,
-                 a.st, a.qfrag, a.idx, a.b, a.e, a.D, a.Q, a.row_scale, a.tau, a.cs, a.ci, a.cc, a.cap, a.dense, a.capq, a.gate);
+    launch_timed(a.gate ? kUntimed : kTimeCosineScore, k_cosine_score<NQB, U, KIND, SCALE>, dim3(a.grid), dim3(kScanThreads),
+                 a.lds, a.st, a.qfrag, a.idx, a.b, a.e, a.D, a.Q, a.row_scale, a.tau, a.cs, a.ci, a.cc, a.cap, a.dense, a.capq,
+                 a.gate);
     EVI_LAUNCH_CHECK();
     return EVI_OK;
+}
+
+// row_scale is a compile-time variant (its load is part of the counted stream).  An e4m3 index always has one: the
+// SCALE kernel reads row_scale without a null test, and cosine_topk_impl refuses an e4m3 index without it (EVI_REQUIRE)
+// before anything is launched, so the unscaled form of those kinds is never instantiated.
+template <int NQB, int U, int KIND>
+static int launch_score_scale(const ScoreArgs& a) {
+    if constexpr (KIND >= kIdxFp8Widen) {
+        return launch_score<NQB, U, KIND, true>(a);
+    } else {
+        return a.row_scale ? launch_score<NQB, U, KIND, true>(a) : launch_score<NQB, U, KIND, false>(a);
+    }
 }
 
 template <int NQB, int KIND>
 static int launch_score_u(int U, const ScoreArgs& a) {
     switch (U) {
-        case 4: return launch_score<NQB, 4, KIND>(a);
-        case 2: return launch_score<NQB, 2, KIND>(a);
-        default: return launch_score<NQB, 1, KIND>(a);
+        case 4: return launch_score_scale<NQB, 4, KIND>(a);
+        case 2: return launch_score_scale<NQB, 2, KIND>(a);
+        default: return launch_score_scale<NQB, 1, KIND>(a);
     }
 }
 
@@ -689,8 +769,9 @@ static int cosine_topk_impl(const float* q, int Q, const void* idx, IndexKind ki
     int32_t* ci = reinterpret_cast<int32_t*>(base + w.id_off);
 
     const int chunks = index_chunks(kind, D);
-    // loads in flight per lane per group: the largest U <= kScanMaxU that leaves an EVEN number of groups
-    // (copy-free ping-pong), else the largest U that divides the row.
+    // loads per lane per group: the largest U <= kScanMaxU that leaves an even number of groups, else the largest U that
+    // divides the row.  The stream loop is copy-free for either parity, so the evenness no longer buys anything by itself;
+    // the rule is kept because every measured leg (D = 768: U = 4 for f32 / f16, U = 2 for e4m3) was measured with it.
     int U = 1;
     for (int cand = kScanMaxU; cand >= 1; cand >>= 1)
         if (chunks % (2 * cand) == 0) { U = cand; break; }
