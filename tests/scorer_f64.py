@@ -1,0 +1,198 @@
+"""Float64 restatement of the edge scorer and its loss, with autograd (test infrastructure only, no test in here).
+
+`oracle/scorer.py`, `oracle/graph.py` and `oracle/loss.py` restated in torch float64: the eval-mode `Retriever` forward
+(projectors, non-text substitution, DDE node structure features, both scoring directions, the bidirectional combine in the
+three direction modes, `edge_bias`) and `RetrieverLoss` (multi-positive InfoNCE, optional BCE, near / bridge edge weights).
+The numpy oracle rounds every step to f32 and has no backward; this one rounds nothing and gets every gradient from
+`torch.autograd`, so it serves as the high-precision reference for any batch — graphs without edges, self loops, unused
+relation ids — that the committed goldens do not contain.  tests/test_scorer_f64_cpu.py pins it to the goldens (the
+reference's own f32 outputs and autograd).
+"""
+from __future__ import annotations
+
+import math
+from typing import Any, Dict, Optional
+
+import numpy as np
+import torch
+
+LN_EPS = 1e-5  # torch.nn.LayerNorm default
+MIN_EDGE_WEIGHT = 1e-6
+F64 = torch.float64
+
+
+def _cpu(a) -> torch.Tensor:
+    return a.detach().cpu() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
+
+
+def _f64(a) -> torch.Tensor:
+    return _cpu(a).to(F64)
+
+
+def _i64(a) -> torch.Tensor:
+    return _cpu(a).to(torch.int64).reshape(-1)
+
+
+def leaf_weights(state_dict: Dict[str, Any]) -> Dict[str, torch.Tensor]:
+    """A `state_dict`-shaped dict (numpy arrays or tensors) as float64 leaves that require grad; integer buffers
+    (`parity_meta`) are left out."""
+    out = {}
+    for k, v in state_dict.items():
+        t = _cpu(v)
+        if t.is_floating_point():
+            out[k] = t.to(F64).clone().requires_grad_(True)
+    return out
+
+
+def _linear(x, w, name):
+    return x @ w[f"{name}.weight"].T + w[f"{name}.bias"]
+
+
+def _layer_norm(x, weight, bias):
+    mu = x.mean(dim=-1, keepdim=True)
+    var = ((x - mu) ** 2).mean(dim=-1, keepdim=True)
+    return (x - mu) / torch.sqrt(var + LN_EPS) * weight + bias
+
+
+def _gelu(x):
+    return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
+
+
+def _projector(x, w, name):
+    return torch.tanh(_linear(x, w, f"{name}.network.0"))
+
+
+def mean_propagate(x: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """out[v] = mean over the edges (u -> v) of x[u], 0 where v has no in-edge (oracle/graph.py: mean_propagate)."""
+    out = torch.zeros_like(x).index_add_(0, dst, x[src])
+    cnt = torch.bincount(dst, minlength=x.size(0)).clamp(min=1).to(F64)
+    return out / cnt[:, None]
+
+
+def node_structure_features(topic_one_hot, edge_index, num_rounds: int, num_reverse_rounds: int, num_topics: int = 2) -> torch.Tensor:
+    """stack([topic, f1.., r1..], -1).reshape(N, -1) in float64 (oracle/graph.py: dde, node_structure_features)."""
+    t = _f64(topic_one_hot)
+    if t.dim() == 1:
+        t = t[:, None]
+    t = t[:, :num_topics]
+    ei = _cpu(edge_index).to(torch.int64)
+    src, dst = ei[0], ei[1]
+    feats = [t]
+    h = t
+    for _ in range(int(num_rounds)):
+        h = mean_propagate(h, src, dst)
+        feats.append(h)
+    h = t
+    for _ in range(int(num_reverse_rounds)):
+        h = mean_propagate(h, dst, src)
+        feats.append(h)
+    return torch.stack(feats, dim=-1).reshape(t.size(0), -1)
+
+
+def _score_edges(w, query_repr, head_repr, relation_repr, tail_repr, struct_raw):
+    gate = torch.sigmoid(_linear(query_repr, w, "q_gate.0"))
+    bias = torch.tanh(_linear(query_repr, w, "q_bias.0"))
+    r_ctx = relation_repr * gate + bias
+    s = _gelu(_layer_norm(_linear(struct_raw, w, "struct_proj.0"), w["struct_proj.1.weight"], w["struct_proj.1.bias"]))
+    nav = torch.sigmoid(_linear(s, w, "struct_gate_net.0"))
+    inter = head_repr * r_ctx * tail_repr * nav
+    err = head_repr + r_ctx - tail_repr
+    dist = -torch.linalg.vector_norm(err, dim=-1, keepdim=True)  # zero subgradient at err == 0, as torch.norm
+    combined = torch.cat([inter, s, err, dist], dim=-1)
+    h = _gelu(_layer_norm(_linear(combined, w, "state_net.0"), w["state_net.1.weight"], w["state_net.1.bias"]))
+    feats = _linear(h, w, "state_net.4")  # state_net.3 (Dropout) is the identity in eval mode
+    return _linear(feats, w, "score_head")[:, 0], feats
+
+
+def edge_graph_ids(edge_index, ptr) -> torch.Tensor:
+    """edge -> graph id: ptr[g] <= head < ptr[g + 1] (oracle/graph.py: compute_edge_batch)."""
+    head = _cpu(edge_index).to(torch.int64)[0].contiguous()
+    return torch.bucketize(head, _i64(ptr)[1:], right=True)
+
+
+def retriever_forward(w: Dict[str, torch.Tensor], batch, *, num_rounds: int, num_reverse_rounds: int,
+                      direction_mode: str = "bidirectional", edge_bias=None) -> Dict[str, Optional[torch.Tensor]]:
+    """Eval-mode forward on a flat batch (attributes as evi_rag_amd.synthetic.SyntheticBatch: numpy arrays or tensors; the
+    relation rows either as `edge_embeddings` [E, D] or as `relation_embedding_table` [R, D] gathered by `edge_attr`).
+    Returns logits, logits_fwd, logits_bwd, edge_embeddings, node_struct, query_ids; differentiable w.r.t. `w`."""
+    ei = _cpu(batch.edge_index).to(torch.int64)
+    head, tail = ei[0], ei[1]
+    query_ids = edge_graph_ids(ei, batch.ptr)
+    query_repr = _projector(_f64(batch.question_emb), w, "query_proj")[query_ids]
+    node_repr = _projector(_f64(batch.node_embeddings), w, "entity_proj")
+    non_text = _projector(w["non_text_entity_emb.weight"], w, "entity_proj")[0]
+    mask = _i64(batch.node_embedding_ids) == 0
+    if bool(mask.any()):
+        node_repr = torch.where(mask[:, None], non_text[None, :], node_repr)
+    head_repr, tail_repr = node_repr[head], node_repr[tail]
+    rows = getattr(batch, "edge_embeddings", None)
+    if rows is None:
+        rows = _f64(batch.relation_embedding_table)[_i64(batch.edge_attr)]
+    relation_repr = _projector(_f64(rows), w, "relation_proj")
+    ns = node_structure_features(batch.topic_one_hot, ei, num_rounds, num_reverse_rounds)
+    lf = ff = lb = fb = None
+    if direction_mode in ("forward", "bidirectional"):
+        lf, ff = _score_edges(w, query_repr, head_repr, relation_repr, tail_repr, torch.cat([ns[head], ns[tail]], dim=-1))
+    if direction_mode in ("backward", "bidirectional"):
+        lb, fb = _score_edges(w, query_repr, tail_repr, relation_repr, head_repr, torch.cat([ns[tail], ns[head]], dim=-1))
+    if edge_bias is not None:  # added to both directional logits before the combine
+        eb = _f64(edge_bias).reshape(-1)
+        lf = None if lf is None else lf + eb
+        lb = None if lb is None else lb + eb
+    if direction_mode == "bidirectional":
+        st = torch.stack([lf, lb], dim=0)
+        wts = torch.softmax(st, dim=0)
+        logits = (wts * st).sum(dim=0)
+        feats = wts[0][:, None] * ff + wts[1][:, None] * fb
+    elif direction_mode == "forward":
+        logits, feats = lf, ff
+    elif direction_mode == "backward":
+        logits, feats = lb, fb
+    else:
+        raise ValueError(f"direction_mode {direction_mode!r}")
+    return {"logits": logits, "logits_fwd": lf, "logits_bwd": lb, "edge_embeddings": feats, "node_struct": ns,
+            "query_ids": query_ids}
+
+
+def retriever_loss(logits: torch.Tensor, targets, edge_batch, num_graphs: int, *, infonce_temperature: float = 1.0,
+                   infonce_weight: float = 1.0, bce_weight: float = 0.0, edge_weight_near: float = 1.0,
+                   edge_weight_bridge: float = 1.0, edge_is_near=None) -> torch.Tensor:
+    """The weighted total of oracle/loss.py: retriever_loss as a differentiable float64 scalar.  InfoNCE: mean over the graphs
+    with at least one positive and one negative edge of logsumexp(all) - logsumexp(positives) of logit / T + log(weight),
+    zero when the batch has no positive or no negative at all; BCE: mean over the graphs with edges (positive weight sum) of
+    the (weighted) mean binary cross entropy with logits."""
+    x = logits.reshape(-1)
+    t = _f64(targets).reshape(-1)
+    eb = _i64(edge_batch)
+    wgt = None
+    if edge_weight_near != 1.0 or edge_weight_bridge != 1.0:
+        near = _cpu(edge_is_near).bool().reshape(-1)
+        wgt = torch.where(near, torch.tensor(float(edge_weight_near), dtype=F64), torch.tensor(float(edge_weight_bridge), dtype=F64))
+    pos = t > 0.5
+    total = x.new_zeros(())
+    if infonce_weight != 0.0 and bool(pos.any()) and bool((~pos).any()):
+        s = x / float(infonce_temperature)
+        if wgt is not None:
+            s = s + torch.log(wgt.clamp(min=MIN_EDGE_WEIGHT))
+        terms = []
+        for g in range(int(num_graphs)):
+            m = eb == g
+            mp = m & pos
+            if bool(mp.any()) and bool((m & ~pos).any()):
+                terms.append(torch.logsumexp(s[m], dim=0) - torch.logsumexp(s[mp], dim=0))
+        if terms:
+            total = total + float(infonce_weight) * torch.stack(terms).mean()
+    if bce_weight > 0.0:
+        per_edge = x.clamp(min=0) - x * t + torch.log1p(torch.exp(-x.abs()))
+        if wgt is not None:
+            per_edge = per_edge * wgt
+        terms = []
+        for g in range(int(num_graphs)):
+            m = eb == g
+            if not bool(m.any()):
+                continue
+            denom = wgt[m].sum().clamp(min=MIN_EDGE_WEIGHT) if wgt is not None else float(int(m.sum()))
+            terms.append(per_edge[m].sum() / denom)
+        if terms:
+            total = total + float(bce_weight) * torch.stack(terms).mean()
+    return total
