@@ -254,12 +254,20 @@ constexpr int kScanThreads = 1024;
 constexpr int kScanMaxU = 4;  // most loads per lane per group
 constexpr int kScanSets = 2;  // register sets of a wave's stream: one group (4 KiB per wave at U = 4) ahead of the MFMAs
 
-template <int NQB, int U, int F16, bool SCALE>
+//   FILTER: row labels and per-query allow-sets.  Row r is visible to query i iff
+//   row_labels[r] < 32 and bit row_labels[r] of query_allow[i] is set.  The label byte of the lane's row is loaded where
+//   row_scale is (one byte per lane n at tile change, behind the next tile's first group) and travels with the stream; the
+//   lane's 4 NQB allow words stay in registers.  A hidden (query, row) pair is never appended, whatever its score (NaN
+//   included) and whatever the threshold (-inf included).  The dense first segment writes every score as before: its
+//   selection (k_candidates_select_filtered) reads the labels itself.  FILTER == false is the unfiltered kernel: the two
+//   trailing arguments are never read.
+template <int NQB, int U, int F16, bool SCALE, bool FILTER = false>
 __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
     const float* __restrict__ qfrag, const void* __restrict__ idx, int64_t seg_begin,
     int64_t seg_end, int D, int Q, const float* __restrict__ row_scale,
     const float* __restrict__ tau, float* __restrict__ cand_score, int32_t* __restrict__ cand_id,
-    int32_t* __restrict__ cand_cnt, int64_t cap, int dense, int capq, const int32_t* __restrict__ gate) {
+    int32_t* __restrict__ cand_cnt, int64_t cap, int dense, int capq, const int32_t* __restrict__ gate,
+    const uint8_t* __restrict__ row_labels, const uint32_t* __restrict__ query_allow) {
     if (gate_closed(gate)) return;
     extern __shared__ float4 lds_q[];  // [(D/16)*4][NQB*16] float4, then the append staging area
     constexpr int NQ = NQB * 16;
@@ -289,6 +297,17 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
             const int qi = b * 16 + 4 * g + r;
             tq[b][r] = qi >= Q ? INFINITY : (dense ? -INFINITY : tau[qi]);
         }
+
+    uint32_t allow[NQB][4];  // FILTER: the allow-sets of this lane's queries (0 for a slot past Q)
+    if (FILTER) {
+#pragma unroll
+        for (int b = 0; b < NQB; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int qi = b * 16 + 4 * g + r;
+                allow[b][r] = qi < Q ? query_allow[qi] : 0u;
+            }
+    }
 
     float qs1[NQB][4], qs2[NQB][4];  // native fp8: the two piece scales of this lane's queries
     if (F16 == 3) {
@@ -401,8 +420,8 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
         }
     };
 
-    // the tile's scores against the thresholds; `scale` is row_scale[row] (SCALE only)
-    auto epilogue = [&](int64_t row, float scale) {
+    // the tile's scores against the thresholds; `scale` is row_scale[row] (SCALE only), `label` is row_labels[row] (FILTER only)
+    auto epilogue = [&](int64_t row, float scale, uint32_t label) {
         float s[NQB][4];
 #pragma unroll
         for (int b = 0; b < NQB; ++b)
@@ -427,11 +446,19 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
             }
             return;
         }
+        const uint32_t label_bit = label < 32u ? 1u << label : 0u;  // FILTER: a label >= 32 matches no query
         bool any = false;  // tq is +inf for a query slot past Q; !(s < tq) also lets a NaN score through
 #pragma unroll
         for (int b = 0; b < NQB; ++b)
 #pragma unroll
             for (int r = 0; r < 4; ++r) any |= !(s[b][r] < tq[b][r]);
+        if (FILTER) {  // the filter wins over a threshold of -inf and over a NaN score
+            any = false;
+#pragma unroll
+            for (int b = 0; b < NQB; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) any |= (allow[b][r] & label_bit) != 0u && !(s[b][r] < tq[b][r]);
+        }
         any &= row < seg_end;
         if (__ballot(any) == 0) return;
         if (!any) return;  // among them the lanes of a ragged last tile whose row lies past the segment
@@ -445,6 +472,7 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
             for (int r = 0; r < 4; ++r) {
                 const int qi = b * 16 + 4 * gq + r;
                 if (qi >= Q || !(s[b][r] >= tq[b][r] || s[b][r] != s[b][r])) continue;
+                if (FILTER && (allow[b][r] & label_bit) == 0u) continue;
                 const int p = atomicAdd(&lds_cnt[qi], 1);
                 if (p < capq) {
                     lds_sc[qi * capq + p] = s[b][r];
@@ -464,10 +492,15 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
         int gl = 0, gm = 0;
         const f32x4* lp = tile_ptr(tl);
         float scale = 1.0f;
+        uint32_t label = 0xFFu;
         auto load_scale = [&]() {
             if (SCALE) {
                 const int64_t r = seg_begin + (int64_t)tm * 16 + n;
                 scale = row_scale[r < seg_end ? r : seg_end - 1];
+            }
+            if (FILTER) {
+                const int64_t r = seg_begin + (int64_t)tm * 16 + n;
+                label = row_labels[r < seg_end ? r : seg_end - 1];
             }
         };
         auto load_next = [&](f32x4 (&x)[U]) {
@@ -491,7 +524,7 @@ __global__ __launch_bounds__(kScanThreads) void k_cosine_score(
             mul_group(cur, gm);
             __builtin_amdgcn_sched_barrier(0);
             if (++gm < groups) return;
-            if (tm < tiles) epilogue(seg_begin + (int64_t)tm * 16 + n, scale);
+            if (tm < tiles) epilogue(seg_begin + (int64_t)tm * 16 + n, scale, label);
             gm = 0;
             tm += stride;
 #pragma unroll
@@ -540,12 +573,18 @@ __device__ inline void write_topk(const SelectShared& sh, int m, int qi, int k, 
 
 // One workgroup per query: exact top-k of its candidate list, written back sorted to the head of
 // the list; raises tau to the k-th score.  The last call of a batch also writes the outputs.
-__global__ __launch_bounds__(kSelectThreads) void k_candidates_select(
+//   FILTER (k_candidates_select_filtered): the dense first segment holds a score for EVERY (query, row) pair, so its
+//   selection reads the row's label beside the score and turns a hidden entry into a key below every real one: high word 0
+//   (the smallest real high word is that of -inf, 0x007FFFFF), low word as for a real key, so the keys stay distinct and
+//   non-zero as block_topk requires.  Sorted, the real keys come first; only those are written back, counted and allowed to
+//   raise tau (k sorted keys are not enough: k REAL keys are needed).  Later segments append visible pairs only, so their
+//   lists hold nothing but real keys.  FILTER == false compiles to the unfiltered kernel.
+template <bool FILTER>
+__device__ __forceinline__ void candidates_select_pass(
     float* __restrict__ cand_score, int32_t* __restrict__ cand_id, int32_t* __restrict__ cand_cnt,
     float* __restrict__ tau, int64_t cap, int k, int64_t dense_count, int final_pass,
     int64_t row_id_base, float* __restrict__ out_score, int64_t* __restrict__ out_index,
-    const int32_t* __restrict__ gate) {
-    if (gate_closed(gate)) return;
+    const uint8_t* __restrict__ row_labels, const uint32_t* __restrict__ query_allow) {
     __shared__ SelectShared sh;
     const int qi = blockIdx.x;
     const float* cs = cand_score + qi * cap;
@@ -555,9 +594,28 @@ __global__ __launch_bounds__(kSelectThreads) void k_candidates_select(
     // 65 536 (score, id) pairs of a dense first segment are 1.5 - 2 MB of reads, most of that selection's 75 us.  In the
     // dense segment entry i IS row i of the shard (the segment starts at row 0), so its ids are never read.
     const bool dense = dense_count >= 0;
-    auto load = [&](int64_t i) -> uint64_t { return make_key(cs[i], dense ? (uint32_t)i : (uint32_t)ci[i]); };
-    const int m = block_topk(sh, load, cnt, k);
+    const uint32_t allow = FILTER ? query_allow[qi] : 0u;
+    auto load = [&](int64_t i) -> uint64_t {
+        const uint64_t key = make_key(cs[i], dense ? (uint32_t)i : (uint32_t)ci[i]);
+        if (FILTER) {
+            // dense entry i is row i of the shard.  The label load is unconditional (row 0 for a later list, whose entries are
+            // all visible), like the loads of block_topk's radix loops: no branch between two keys' loads
+            const uint32_t label = row_labels[dense ? i : 0];
+            const bool hidden = dense && (label >= 32u || ((allow >> label) & 1u) == 0u);
+            return hidden ? key & 0xFFFFFFFFull : key;  // hidden: below every real key
+        }
+        return key;
+    };
+    int m = block_topk(sh, load, cnt, k);
     // block_topk ends on a barrier: every read of the old list is done before it is overwritten.
+    if (FILTER && dense) {  // keep the real keys of the m sorted ones: they come first
+        if (threadIdx.x == 0) sh.scalar[3] = 0;
+        __syncthreads();
+        for (int i = threadIdx.x; i < m; i += blockDim.x)
+            if ((sh.keys[i] >> 32) != 0ull && (i + 1 == m || (sh.keys[i + 1] >> 32) == 0ull)) sh.scalar[3] = (uint32_t)(i + 1);
+        __syncthreads();
+        m = (int)sh.scalar[3];
+    }
     for (int i = threadIdx.x; i < m; i += blockDim.x) {
         const uint64_t key = sh.keys[i];
         cand_score[qi * cap + i] = key_score(key);
@@ -568,6 +626,26 @@ __global__ __launch_bounds__(kSelectThreads) void k_candidates_select(
         if (m == k) tau[qi] = key_score(sh.keys[k - 1]);
     }
     if (final_pass) write_topk(sh, m, qi, k, row_id_base, out_score, out_index);
+}
+
+__global__ __launch_bounds__(kSelectThreads) void k_candidates_select(
+    float* __restrict__ cand_score, int32_t* __restrict__ cand_id, int32_t* __restrict__ cand_cnt,
+    float* __restrict__ tau, int64_t cap, int k, int64_t dense_count, int final_pass,
+    int64_t row_id_base, float* __restrict__ out_score, int64_t* __restrict__ out_index,
+    const int32_t* __restrict__ gate) {
+    if (gate_closed(gate)) return;
+    candidates_select_pass<false>(cand_score, cand_id, cand_cnt, tau, cap, k, dense_count, final_pass, row_id_base, out_score,
+                                  out_index, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kSelectThreads) void k_candidates_select_filtered(
+    float* __restrict__ cand_score, int32_t* __restrict__ cand_id, int32_t* __restrict__ cand_cnt,
+    float* __restrict__ tau, int64_t cap, int k, int64_t dense_count, int final_pass,
+    int64_t row_id_base, float* __restrict__ out_score, int64_t* __restrict__ out_index,
+    const int32_t* __restrict__ gate, const uint8_t* __restrict__ row_labels, const uint32_t* __restrict__ query_allow) {
+    if (gate_closed(gate)) return;
+    candidates_select_pass<true>(cand_score, cand_id, cand_cnt, tau, cap, k, dense_count, final_pass, row_id_base, out_score,
+                                 out_index, row_labels, query_allow);
 }
 
 struct WsLayout {
@@ -609,22 +687,30 @@ struct ScoreArgs {
     int64_t cap;
     int dense, capq;
     const int32_t* gate;
+    const uint8_t* row_labels;    // both null: the unfiltered kernels
+    const uint32_t* query_allow;  // the allow-sets of this pass's queries
 };
 
-template <int NQB, int U, int KIND, bool SCALE>
+template <int NQB, int U, int KIND, bool SCALE, bool FILTER>
 static int launch_score(const ScoreArgs& a) {
     static thread_local bool attr_set = false;
     if (!attr_set) {
-        EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cosine_score<NQB, U, KIND, SCALE>),
+        EVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cosine_score<NQB, U, KIND, SCALE, FILTER>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
     // gated launches (the fallback of a proof-carrying path) stay out of the timing accounts
-    launch_timed(a.gate ? kUntimed : kTimeCosineScore, k_cosine_score<NQB, U, KIND, SCALE>, dim3(a.grid), dim3(kScanThreads),
-                 a.lds, a.st, a.qfrag, a.idx, a.b, a.e, a.D, a.Q, a.row_scale, a.tau, a.cs, a.ci, a.cc, a.cap, a.dense, a.capq,
-                 a.gate);
+    launch_timed(a.gate ? kUntimed : kTimeCosineScore, k_cosine_score<NQB, U, KIND, SCALE, FILTER>, dim3(a.grid),
+                 dim3(kScanThreads), a.lds, a.st, a.qfrag, a.idx, a.b, a.e, a.D, a.Q, a.row_scale, a.tau, a.cs, a.ci, a.cc, a.cap,
+                 a.dense, a.capq, a.gate, a.row_labels, a.query_allow);
     EVI_LAUNCH_CHECK();
     return EVI_OK;
+}
+
+// the filter is a compile-time variant like row_scale: a call without labels launches the FILTER = false instantiation
+template <int NQB, int U, int KIND, bool SCALE>
+static int launch_score_filter(const ScoreArgs& a) {
+    return a.row_labels ? launch_score<NQB, U, KIND, SCALE, true>(a) : launch_score<NQB, U, KIND, SCALE, false>(a);
 }
 
 // row_scale is a compile-time variant (its load is part of the counted stream).  An e4m3 index always has one: the
@@ -633,9 +719,9 @@ static int launch_score(const ScoreArgs& a) {
 template <int NQB, int U, int KIND>
 static int launch_score_scale(const ScoreArgs& a) {
     if constexpr (KIND >= kIdxFp8Widen) {
-        return launch_score<NQB, U, KIND, true>(a);
+        return launch_score_filter<NQB, U, KIND, true>(a);
     } else {
-        return a.row_scale ? launch_score<NQB, U, KIND, true>(a) : launch_score<NQB, U, KIND, false>(a);
+        return a.row_scale ? launch_score_filter<NQB, U, KIND, true>(a) : launch_score_filter<NQB, U, KIND, false>(a);
     }
 }
 
@@ -732,7 +818,9 @@ extern "C" size_t evi_cosine_topk_min_workspace_bytes(int Q, int64_t N, int D, i
 static int cosine_topk_impl(const float* q, int Q, const void* idx, IndexKind kind, int64_t N, int D,
                             const float* row_scale, int k, int64_t row_id_base, float* out_score,
                             int64_t* out_index, void* workspace, size_t workspace_bytes, void* stream,
-                            const int32_t* gate = nullptr) {
+                            const int32_t* gate = nullptr, const uint8_t* row_labels = nullptr,
+                            const uint32_t* query_allow = nullptr) {
+    EVI_REQUIRE((row_labels == nullptr) == (query_allow == nullptr), "evi_cosine_topk: row_labels and query_allow go together");
     EVI_REQUIRE(Q >= 1, "evi_cosine_topk: Q must be >= 1, got %d", Q);
     EVI_REQUIRE(N >= 0, "evi_cosine_topk: N must be >= 0, got %lld", (long long)N);
     EVI_REQUIRE(N < (int64_t)0x7FFFFFFF, "evi_cosine_topk: a shard holds at most 2^31-1 rows, got %lld",
@@ -816,13 +904,19 @@ static int cosine_topk_impl(const float* q, int Q, const void* idx, IndexKind ki
             const int64_t tiles = (end - begin + 15) / 16;
             int64_t want = (tiles + waves_per_block - 1) / waves_per_block;
             const int grid = (int)(want < cus ? want : cus);
+            const uint32_t* allow = query_allow ? query_allow + q0 : nullptr;
             const ScoreArgs sa{grid, lds, st, qfrag, idx, begin, end, D, qn, row_scale, tau,
-                               cs, ci, cnt, w.cap, first ? 1 : 0, capq, gate};
+                               cs, ci, cnt, w.cap, first ? 1 : 0, capq, gate, row_labels, allow};
             const int rc = launch_score_kind(kind, nqb, U, sa);
             if (rc != EVI_OK) return rc;
             const int final_pass = end >= N ? 1 : 0;
-            launch_timed(gate ? kUntimed : kTimeSelect, k_candidates_select, dim3(qn), dim3(kSelectThreads), 0, st, cs, ci, cnt,
-                         tau, w.cap, k, first ? (end - begin) : (int64_t)-1, final_pass, row_id_base, o_score, o_index, gate);
+            if (row_labels)
+                launch_timed(gate ? kUntimed : kTimeSelect, k_candidates_select_filtered, dim3(qn), dim3(kSelectThreads), 0, st, cs,
+                             ci, cnt, tau, w.cap, k, first ? (end - begin) : (int64_t)-1, final_pass, row_id_base, o_score, o_index,
+                             gate, row_labels, allow);
+            else
+                launch_timed(gate ? kUntimed : kTimeSelect, k_candidates_select, dim3(qn), dim3(kSelectThreads), 0, st, cs, ci, cnt,
+                             tau, w.cap, k, first ? (end - begin) : (int64_t)-1, final_pass, row_id_base, o_score, o_index, gate);
             EVI_LAUNCH_CHECK();
             begin = end;
             first = false;
@@ -863,6 +957,17 @@ extern "C" int evi_cosine_topk_fp8_mfma(const float* q, int Q, const void* idx_f
                                         int64_t* out_index, void* workspace, size_t workspace_bytes, void* stream) {
     return cosine_topk_impl(q, Q, idx_fp8, kIdxFp8Mfma, N, D, row_scale, k, row_id_base, out_score, out_index, workspace,
                             workspace_bytes, stream);
+}
+
+extern "C" int evi_cosine_topk_filtered(const float* q, int Q, const void* idx, int kind, int64_t N, int D,
+                                        const float* row_scale, const uint8_t* row_labels, const uint32_t* query_allow, int k,
+                                        int64_t row_id_base, float* out_score, int64_t* out_index, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    EVI_REQUIRE(kind >= kIdxF32 && kind <= kIdxFp8Mfma, "evi_cosine_topk_filtered: kind must be 0 (f32), 1 (f16), 2 (e4m3 widened) "
+                "or 3 (e4m3 native MFMA), got %d", kind);
+    EVI_REQUIRE(row_labels && query_allow, "evi_cosine_topk_filtered: null row_labels / query_allow");
+    return cosine_topk_impl(q, Q, idx, (IndexKind)kind, N, D, row_scale, k, row_id_base, out_score, out_index, workspace,
+                            workspace_bytes, stream, nullptr, row_labels, query_allow);
 }
 
 // =====================================================================================================
@@ -1488,9 +1593,10 @@ extern "C" size_t evi_cosine_topk_two_stage_workspace_bytes(int Q, int64_t N, in
     return ts_layout(Q, N, D, k).total;
 }
 
-extern "C" int evi_cosine_topk_two_stage(const float* q, int Q, const float* idx, const void* shadow_f16, int64_t N, int D,
-                                         int k, int64_t row_id_base, float* out_score, int64_t* out_index, int32_t* status,
-                                         int device_fallback, void* workspace, size_t workspace_bytes, void* stream) {
+static int cosine_topk_two_stage_impl(const float* q, int Q, const float* idx, const void* shadow_f16, int64_t N, int D,
+                                      const uint8_t* row_labels, const uint32_t* query_allow, int k, int64_t row_id_base,
+                                      float* out_score, int64_t* out_index, int32_t* status, int device_fallback, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
     EVI_REQUIRE(Q >= 1 && N >= 1, "evi_cosine_topk_two_stage: need Q >= 1 and N >= 1, got Q=%d N=%lld", Q, (long long)N);
     EVI_REQUIRE(k >= 1, "evi_cosine_topk_two_stage: k must be >= 1, got %d", k);
     if (D < 32 || D % 32 != 0 || D > 1280)
@@ -1513,7 +1619,8 @@ extern "C" int evi_cosine_topk_two_stage(const float* q, int Q, const float* idx
     int32_t* call_flag = reinterpret_cast<int32_t*>(base + L.flag);
     EVI_HIP_CHECK(hipMemsetAsync(call_flag, 0, sizeof(int32_t), st));
     // stage 1: kk best rows per query by shadow score (local row ids)
-    const int rc = cosine_topk_impl(q, Q, shadow_f16, kIdxF16, N, D, nullptr, kk, 0, approx, ids, base + L.scan, L.scan_bytes, stream);
+    const int rc = cosine_topk_impl(q, Q, shadow_f16, kIdxF16, N, D, nullptr, kk, 0, approx, ids, base + L.scan, L.scan_bytes, stream,
+                                    nullptr, row_labels, query_allow);
     if (rc != EVI_OK) return rc;
     // stage 2: exact scores from the f32 rows, final top-k + proof
     launch_rescore<float>(kTimeSelect, st, q, D, idx, nullptr, ids, kk, nullptr, Q, kk, exact);
@@ -1526,8 +1633,27 @@ extern "C" int evi_cosine_topk_two_stage(const float* q, int Q, const float* idx
         // later work of the stream can read it.  No read-back, no agreement between ranks needed: each shard's record is
         // exact when it leaves the device.  The stage-1 scan workspace is free again and large enough (kk >= k).
         const int rc2 = cosine_topk_impl(q, Q, idx, kIdxF32, N, D, nullptr, k, row_id_base, out_score, out_index, base + L.scan,
-                                         L.scan_bytes, stream, call_flag);
+                                         L.scan_bytes, stream, call_flag, row_labels, query_allow);
         if (rc2 != EVI_OK) return rc2;
     }
     return EVI_OK;
+}
+
+extern "C" int evi_cosine_topk_two_stage(const float* q, int Q, const float* idx, const void* shadow_f16, int64_t N, int D,
+                                         int k, int64_t row_id_base, float* out_score, int64_t* out_index, int32_t* status,
+                                         int device_fallback, void* workspace, size_t workspace_bytes, void* stream) {
+    return cosine_topk_two_stage_impl(q, Q, idx, shadow_f16, N, D, nullptr, nullptr, k, row_id_base, out_score, out_index, status,
+                                      device_fallback, workspace, workspace_bytes, stream);
+}
+
+// The filter goes to the stage-1 shadow scan (the kk kept rows are the best VISIBLE rows by shadow score, so the proof is
+// the unfiltered one over the visible rows) and to the gated f32 fallback scan; the re-scoring, the gap test and the final
+// selection see a shorter or -1 padded list exactly as they do for a short index.
+extern "C" int evi_cosine_topk_two_stage_filtered(const float* q, int Q, const float* idx, const void* shadow_f16, int64_t N,
+                                                  int D, const uint8_t* row_labels, const uint32_t* query_allow, int k,
+                                                  int64_t row_id_base, float* out_score, int64_t* out_index, int32_t* status,
+                                                  int device_fallback, void* workspace, size_t workspace_bytes, void* stream) {
+    EVI_REQUIRE(row_labels && query_allow, "evi_cosine_topk_two_stage_filtered: null row_labels / query_allow");
+    return cosine_topk_two_stage_impl(q, Q, idx, shadow_f16, N, D, row_labels, query_allow, k, row_id_base, out_score, out_index,
+                                      status, device_fallback, workspace, workspace_bytes, stream);
 }

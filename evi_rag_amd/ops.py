@@ -86,6 +86,42 @@ def _topk_out(out: Optional[Tuple[torch.Tensor, torch.Tensor]], Q: int, k: int, 
     return out_score, out_index
 
 
+def _check_topk_filter(row_mask, row_labels, query_allow, N: int, Q: int) -> bool:
+    """Validates the row-filter keywords of the top-k entry points (argument rules only: no device work, so it runs
+    before the device check).  True when a filter is given."""
+    if row_mask is None and row_labels is None and query_allow is None:
+        return False
+    if row_mask is not None and row_labels is not None:
+        raise ValueError("row_mask and row_labels are two spellings of one filter: give one of them")
+    if query_allow is not None and row_labels is None:
+        raise ValueError("query_allow goes with row_labels (row_mask allows the same rows to every query)")
+    if row_labels is not None and query_allow is None:
+        raise ValueError("row_labels needs query_allow (one 32-bit set of allowed labels per query)")
+    if row_mask is not None:
+        if row_mask.dtype != torch.bool or row_mask.dim() != 1 or row_mask.numel() != N:
+            raise ValueError(f"row_mask must be a bool tensor of length N = {N}, got {row_mask.dtype} {tuple(row_mask.shape)}")
+        return True
+    if row_labels.dtype != torch.uint8 or row_labels.dim() != 1 or row_labels.numel() != N:
+        raise ValueError(f"row_labels must be a uint8 tensor of length N = {N}, got {row_labels.dtype} {tuple(row_labels.shape)}")
+    if query_allow.dtype not in (torch.int32, torch.int64) or query_allow.dim() != 1 or query_allow.numel() != Q:
+        raise ValueError(f"query_allow must be an int32 or int64 tensor of length Q = {Q}, got {query_allow.dtype} "
+                         f"{tuple(query_allow.shape)}")
+    return True
+
+
+def _topk_filter_operands(row_mask, row_labels, query_allow, Q: int, dev: torch.device):
+    """(labels uint8 [N], allow int32 [Q] holding the 32 set bits) as evi_cosine_topk_filtered takes them.  A bool mask's
+    storage already is a 0/1 label array; its allow-set is {1} for every query.  int64 allow-sets keep their low 32 bits
+    (values in [0, 2^32)); int32 ones are taken bit for bit."""
+    if row_mask is not None:
+        return row_mask.contiguous().view(torch.uint8), torch.full((Q,), 2, dtype=torch.int32, device=dev)
+    allow = query_allow
+    if allow.dtype == torch.int64:
+        low = allow & 0xFFFFFFFF
+        allow = torch.where(low >= 2 ** 31, low - 2 ** 32, low).to(torch.int32)
+    return row_labels.contiguous(), allow.contiguous()
+
+
 def _workspace(dev: torch.device, tag: str, nbytes: int) -> torch.Tensor:
     """Grow-only per-(device, tag) scratch buffer (mirrors the reference's grow-only pinned
     buffers, src/data/components/embedding_store.py:101-150, but in HBM)."""
@@ -184,6 +220,9 @@ def cosine_topk(
     out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
     method: str = "auto",
     fp8_mfma: Optional[bool] = None,
+    row_mask: Optional[torch.Tensor] = None,
+    row_labels: Optional[torch.Tensor] = None,
+    query_allow: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k rows of `index` per query by dot product (cosine when both are L2-normalised, or when
     `index` is raw and row_scale = row_inv_norm(index)).  Returns (scores [Q,k] f32, ids [Q,k] i64),
@@ -203,9 +242,22 @@ def cosine_topk(
     fp8_mfma (e4m3 index only; default None = True): feed the index bytes to the native fp8 matrix instruction with the
     query as two e4m3 pieces (evi_cosine_topk_fp8_mfma) — no conversion work on the stream (5.86 vs 5.43 TB/s); scores
     carry 16 significant query bits, ~20x inside the index's own quantisation noise (overlap@500 with the widening
-    variant 0.999).  False: widen the index bytes to f16 in registers and keep the f32 query exact."""
+    variant 0.999).  False: widen the index bytes to f16 in registers and keep the f32 query exact.
+    Row filter (all index kinds; one label byte per row is read beside the index stream, nothing is copied):
+      row_labels (uint8 [N]) + query_allow (int32 / int64 [Q], one 32-bit set per query, values in [0, 2^32)): row r is
+          visible to query i iff row_labels[r] < 32 and bit row_labels[r] of query_allow[i] is set.  A label >= 32 matches
+          no query (tombstone).  Nothing is validated on the device or read back.
+      row_mask (bool [N]): shorthand for labels = the mask's 0 / 1 bytes and allow-set {1} for every query.
+      The result is the exact top-k of the visible rows — the ids and the score bits of cosine_topk on the compacted
+      index, mapped back — with (-inf, -1) past the number of visible rows; a hidden row never appears, NaN score or not.
+      With a filter "auto" takes the two-stage scan when the f16 shadow is resident and the scan otherwise, never the
+      GEMM-shaped pass, and method="gemm" raises ValueError: a filtered many-query pass is not part of this library yet,
+      so Q >= 96 with a filter pays one scan of the index per 32 queries."""
     if method not in ("scan", "gemm", "auto"):
         raise ValueError(f"method must be 'scan', 'gemm' or 'auto', got {method!r}")
+    if row_mask is not None or row_labels is not None or query_allow is not None:
+        return _cosine_topk_filtered(queries, index, k, row_scale, row_id_base, workspace, out, method, fp8_mfma, row_mask,
+                                     row_labels, query_allow)
     if method == "gemm" and index.dtype == torch.uint8 and queries.dim() == 2 and index.dim() == 2:
         cosine_topk.last_method = "gemm"
         return cosine_topk_gemm(queries, index, k, row_scale=row_scale, row_id_base=row_id_base, out=out, fp8_mfma=fp8_mfma)
@@ -246,6 +298,47 @@ def cosine_topk(
             _stream(dev),
         )
     )
+    return out_score, out_index
+
+
+def _cosine_topk_filtered(queries, index, k, row_scale, row_id_base, workspace, out, method, fp8_mfma, row_mask, row_labels,
+                          query_allow):
+    """cosine_topk with a row filter (see there): the two-stage scan or the scan, through the filtered entry points."""
+    if method == "gemm":
+        raise ValueError("method='gemm' takes no row filter: the GEMM-shaped many-query pass has no filtered form "
+                         "(use 'auto' or 'scan')")
+    if queries.dim() != 2 or index.dim() != 2:
+        raise ValueError("queries and index must be 2D")
+    _check_topk_filter(row_mask, row_labels, query_allow, index.size(0), queries.size(0))
+    shadow = resident_shadow_f16(index) if (method == "auto" and row_scale is None and index.dtype == torch.float32) else None
+    if shadow is not None and queries.size(0) >= 1 and index.size(0) >= 1 and _reserve_fits(k) and index.size(1) % 32 == 0 \
+            and queries.dtype == torch.float32 and queries.size(1) == index.size(1):
+        cosine_topk.last_method = "two_stage"
+        return cosine_topk_two_stage(queries, index, shadow, k, row_id_base=row_id_base, out=out, fallback="device",
+                                     row_mask=row_mask, row_labels=row_labels, query_allow=query_allow)
+    cosine_topk.last_method = "scan"
+    dev = _require_gpu(queries, index, row_scale, workspace, row_mask, row_labels, query_allow)
+    if index.dtype == torch.uint8 and row_scale is None:
+        raise ValueError("an fp8 index needs row_scale (the per-row scale returned by quantize_rows_fp8)")
+    q, x, row_scale = _topk_operands(queries, index, row_scale)
+    Q, D = q.shape
+    N = x.shape[0]
+    if Q == 0 or N == 0:  # nothing to hide
+        return cosine_topk(q, x, k, row_scale=row_scale, row_id_base=row_id_base, workspace=workspace, out=out, method="scan",
+                           fp8_mfma=fp8_mfma)
+    labels, allow = _topk_filter_operands(row_mask, row_labels, query_allow, Q, dev)
+    lib = _lib.load()
+    if workspace is None:
+        workspace = _workspace(dev, "cosine_topk", int(lib.evi_cosine_topk_workspace_bytes(Q, N, D, int(k))))
+    out_score, out_index = _topk_out(out, Q, k, dev)
+    if fp8_mfma and x.dtype != torch.uint8:
+        raise ValueError("fp8_mfma goes with an e4m3 (uint8) index")
+    if fp8_mfma is None:
+        fp8_mfma = x.dtype == torch.uint8
+    kind = {torch.float16: 1, torch.uint8: 3 if fp8_mfma else 2}.get(x.dtype, 0)
+    _lib.check(lib.evi_cosine_topk_filtered(_ptr(q), Q, _ptr(x), kind, N, D, _ptr(row_scale), _ptr(labels), _ptr(allow), int(k),
+                                            int(row_id_base), _ptr(out_score), _ptr(out_index), workspace.data_ptr(),
+                                            _nbytes(workspace), _stream(dev)))
     return out_score, out_index
 
 
@@ -501,7 +594,9 @@ def drop_shadow_f16(index: torch.Tensor) -> None:
 
 def cosine_topk_two_stage(queries: torch.Tensor, index: torch.Tensor, shadow: torch.Tensor, k: int, *, row_id_base: int = 0,
                           fallback="device", out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-                          status: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, check_norms: bool = True):
+                          status: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, check_norms: bool = True,
+                          row_mask: Optional[torch.Tensor] = None, row_labels: Optional[torch.Tensor] = None,
+                          query_allow: Optional[torch.Tensor] = None):
     """cosine_topk over an L2-normalised f32 index at half the HBM bytes (see evi_cosine_topk_two_stage): the f16
     `shadow` (index_shadow_f16(index)) is scanned to select k + max(256, k/2) candidates per query, which are re-scored
     from the f32 rows with the scan's arithmetic; ids and scores equal cosine_topk(queries, index, k) bit for bit.
@@ -512,14 +607,21 @@ def cosine_topk_two_stage(queries: torch.Tensor, index: torch.Tensor, shadow: to
         records that a fallback ran.
       fallback="host": the flag is read back (one synchronisation) and the scan is run from the host if needed.
       fallback=False: with status=None the flag is read back and RuntimeError raised on failure; with a `status` tensor
-        nothing is read back and the CALLER must check it before using the outputs (the raw C-ABI contract)."""
+        nothing is read back and the CALLER must check it before using the outputs (the raw C-ABI contract).
+    row_mask / row_labels / query_allow: the row filter of cosine_topk (see there); the result equals the filtered scan
+    bit for bit.  The filter goes to the shadow scan and to every form of the fallback scan."""
     if fallback is True:
         fallback = "device"
     if fallback not in ("device", "host", False):
         raise ValueError(f"fallback must be 'device', 'host' or False, got {fallback!r}")
     if fallback == "host" and status is not None:
         raise ValueError("fallback='host' reads the flag back itself: do not pass status")
-    dev = _require_gpu(queries, index, shadow, status, workspace)
+    filtered = row_mask is not None or row_labels is not None or query_allow is not None
+    if filtered:  # the argument rules come before the device check, as in cosine_topk
+        if queries.dim() != 2 or index.dim() != 2:
+            raise ValueError("queries and index must be 2D")
+        _check_topk_filter(row_mask, row_labels, query_allow, index.size(0), queries.size(0))
+    dev = _require_gpu(queries, index, shadow, status, workspace, row_mask, row_labels, query_allow)
     if queries.dim() != 2 or index.dim() != 2:
         raise ValueError("queries and index must be 2D")
     if index.dtype != torch.float32 or shadow.dtype != torch.float16 or shadow.shape != index.shape or not shadow.is_contiguous():
@@ -536,6 +638,8 @@ def cosine_topk_two_stage(queries: torch.Tensor, index: torch.Tensor, shadow: to
         raise ValueError("status must be an int32 tensor with one element")
     if Q == 0 or N == 0:
         return cosine_topk(q, x, k, row_id_base=row_id_base, out=out, method="scan")
+    labels, allow = _topk_filter_operands(row_mask, row_labels, query_allow, Q, dev) if filtered else (None, None)
+    flt = {"row_labels": labels, "query_allow": allow} if filtered else {}  # for a scan run from the host
     lib = _lib.load()
     need = int(lib.evi_cosine_topk_two_stage_workspace_bytes(Q, N, D, int(k)))
     if need == 0:
@@ -546,9 +650,14 @@ def cosine_topk_two_stage(queries: torch.Tensor, index: torch.Tensor, shadow: to
     flag = status
     if flag is None and not on_device:
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.evi_cosine_topk_two_stage(_ptr(q), Q, _ptr(x), _ptr(shadow), N, D, int(k), int(row_id_base), _ptr(out_score),
-                                             _ptr(out_index), _ptr(flag), 1 if on_device else 0, ws.data_ptr(),
-                                             _nbytes(ws), _stream(dev)))
+    if filtered:
+        _lib.check(lib.evi_cosine_topk_two_stage_filtered(_ptr(q), Q, _ptr(x), _ptr(shadow), N, D, _ptr(labels), _ptr(allow), int(k),
+                                                          int(row_id_base), _ptr(out_score), _ptr(out_index), _ptr(flag),
+                                                          1 if on_device else 0, ws.data_ptr(), _nbytes(ws), _stream(dev)))
+    else:
+        _lib.check(lib.evi_cosine_topk_two_stage(_ptr(q), Q, _ptr(x), _ptr(shadow), N, D, int(k), int(row_id_base), _ptr(out_score),
+                                                 _ptr(out_index), _ptr(flag), 1 if on_device else 0, ws.data_ptr(),
+                                                 _nbytes(ws), _stream(dev)))
     if on_device or status is not None:
         return out_score, out_index
     st = int(flag.item())
@@ -556,7 +665,7 @@ def cosine_topk_two_stage(queries: torch.Tensor, index: torch.Tensor, shadow: to
     if st != 0:
         if fallback is False:
             raise RuntimeError(f"evi_cosine_topk_two_stage could not prove exactness (status {st}): run cosine_topk")
-        return cosine_topk(q, x, k, row_id_base=row_id_base, out=out, method="scan")
+        return cosine_topk(q, x, k, row_id_base=row_id_base, out=out, method="scan", **flt)
     return out_score, out_index
 
 

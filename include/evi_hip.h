@@ -143,6 +143,20 @@ int evi_cosine_topk_fp8_mfma(const float* q, int Q, const void* idx_fp8, int64_t
                              const float* row_scale, int k, int64_t row_id_base, float* out_score,
                              int64_t* out_index, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The exact scans above restricted by row labels and per-query allow-sets, for all four index kinds:
+ *   kind         0 evi_cosine_topk, 1 evi_cosine_topk_f16, 2 evi_cosine_topk_fp8, 3 evi_cosine_topk_fp8_mfma (idx as there)
+ *   row_labels   [N] u8   one label per index row (device)
+ *   query_allow  [Q] u32  one set of labels per query (device)
+ * Row r is visible to query i iff row_labels[r] < 32 and bit row_labels[r] of query_allow[i] is set; a label >= 32
+ * matches no query (a tombstone), nothing is validated or read back.  The result is the exact top-k of the VISIBLE rows,
+ * ordered (score desc, row id asc), slots past the number of visible rows filled with (-inf, -1); a row's score is the
+ * same bits the unfiltered call gives it.  A hidden row never appears, whatever its score (NaN included).  One byte per
+ * row is read beside the index stream; the workspace is that of the unfiltered call (evi_cosine_topk_workspace_bytes).
+ * A null row_labels or query_allow, or a kind outside 0..3, is EVI_ERR_INVALID (checked before any launch). */
+int evi_cosine_topk_filtered(const float* q, int Q, const void* idx, int kind, int64_t N, int D, const float* row_scale,
+                             const uint8_t* row_labels, const uint32_t* query_allow, int k, int64_t row_id_base,
+                             float* out_score, int64_t* out_index, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The same result as evi_cosine_topk (ids and scores bit-identical) for MANY queries (Q in the hundreds; f32
  * index, rows of unit norm after row_scale, D % 16 == 0, k <= 1365): the scores of all queries against a
  * slab of rows are formed as one split-bf16 MFMA GEMM and used only to SELECT k + reserve candidates per
@@ -209,6 +223,14 @@ size_t evi_cosine_topk_two_stage_workspace_bytes(int Q, int64_t N, int D, int k)
 int evi_cosine_topk_two_stage(const float* q, int Q, const float* idx, const void* shadow_f16, int64_t N, int D,
                               int k, int64_t row_id_base, float* out_score, int64_t* out_index, int32_t* status,
                               int device_fallback, void* workspace, size_t workspace_bytes, void* stream);
+/* evi_cosine_topk_two_stage restricted by row labels and allow-sets (see evi_cosine_topk_filtered): the result of
+ * evi_cosine_topk_filtered with kind 0, bit for bit.  The filter goes to the stage-1 shadow scan and to the gated f32
+ * fallback scan; a query with fewer than k + reserve visible rows has all of them in its list and needs no proof.
+ * Same workspace as the unfiltered call.  A null row_labels or query_allow is EVI_ERR_INVALID. */
+int evi_cosine_topk_two_stage_filtered(const float* q, int Q, const float* idx, const void* shadow_f16, int64_t N, int D,
+                                       const uint8_t* row_labels, const uint32_t* query_allow, int k, int64_t row_id_base,
+                                       float* out_score, int64_t* out_index, int32_t* status, int device_fallback,
+                                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* Merge P per-shard top-k lists (the all-gathered outputs of evi_cosine_topk on P ranks) into
  * the global top-k, same (score desc, id asc) order; ids < 0 are padding and never win.
