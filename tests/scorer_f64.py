@@ -2,7 +2,8 @@
 
 `oracle/scorer.py`, `oracle/graph.py` and `oracle/loss.py` restated in torch float64: the eval-mode `Retriever` forward
 (projectors, non-text substitution, DDE node structure features, both scoring directions, the bidirectional combine in the
-three direction modes, `edge_bias`) and `RetrieverLoss` (multi-positive InfoNCE, optional BCE, near / bridge edge weights).
+three direction modes, `edge_bias`, and the training-mode dropout of `state_net` given its mask: `dropout_mul`, with the
+kernel's own mask restated by `_dropout_multipliers`) and `RetrieverLoss` (multi-positive InfoNCE, optional BCE, near / bridge edge weights).
 The numpy oracle rounds every step to f32 and has no backward; this one rounds nothing and gets every gradient from
 `torch.autograd`, so it serves as the high-precision reference for any batch — graphs without edges, self loops, unused
 relation ids — that the committed goldens do not contain.  tests/test_scorer_f64_cpu.py pins it to the goldens (the
@@ -89,7 +90,27 @@ def node_structure_features(topic_one_hot, edge_index, num_rounds: int, num_reve
     return torch.stack(feats, dim=-1).reshape(t.size(0), -1)
 
 
-def _score_edges(w, query_repr, head_repr, relation_repr, tail_repr, struct_raw):
+def _dropout_multipliers(seed, E, H, p):
+    """The kernel's dropout mask restated with numpy integers (csrc/scorer.hip: dropout_mul4): [2, E, H] multipliers, 0 or
+    65536 / (65536 - round(65536 p)).  Row `dir * E + e` of the hash belongs to direction `dir` (0 = forward scoring,
+    1 = backward scoring) of edge e, e counted over the whole batch, E the batch's edge count.  With `direction_mode`
+    "forward" or "backward" alone the kernels (k_state_combine, k_combine_bwd) still hash the loop index `dir` of the one
+    direction they run, not the row it takes in their outputs: a backward-only model reads rows E .. 2E - 1, i.e. [1] here,
+    and a forward-only model rows 0 .. E - 1, i.e. [0] — the slices `retriever_forward(dropout_mul=)` applies."""
+    thr = min(int(round(p * 65536.0)), 65535)
+    scale = np.float32(65536.0 / (65536 - thr))
+    rows = np.arange(2 * E, dtype=np.uint64)[:, None]
+    quads = np.arange(H // 4, dtype=np.uint64)[None, :]
+    with np.errstate(over="ignore"):
+        z = np.uint64(seed) + np.uint64(0x9E3779B97F4A7C15) * (rows * np.uint64(H // 4) + quads + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    u = np.stack([(z >> np.uint64(16 * c)) & np.uint64(0xFFFF) for c in range(4)], axis=-1).reshape(2 * E, H)
+    return np.where(u >= thr, scale, np.float32(0)).astype(np.float32).reshape(2, E, H)
+
+
+def _score_edges(w, query_repr, head_repr, relation_repr, tail_repr, struct_raw, dropout_mul=None):
     gate = torch.sigmoid(_linear(query_repr, w, "q_gate.0"))
     bias = torch.tanh(_linear(query_repr, w, "q_bias.0"))
     r_ctx = relation_repr * gate + bias
@@ -100,7 +121,9 @@ def _score_edges(w, query_repr, head_repr, relation_repr, tail_repr, struct_raw)
     dist = -torch.linalg.vector_norm(err, dim=-1, keepdim=True)  # zero subgradient at err == 0, as torch.norm
     combined = torch.cat([inter, s, err, dist], dim=-1)
     h = _gelu(_layer_norm(_linear(combined, w, "state_net.0"), w["state_net.1.weight"], w["state_net.1.bias"]))
-    feats = _linear(h, w, "state_net.4")  # state_net.3 (Dropout) is the identity in eval mode
+    if dropout_mul is not None:  # state_net.3 (Dropout) with an explicit mask; the identity in eval mode
+        h = h * _f64(dropout_mul)
+    feats = _linear(h, w, "state_net.4")
     return _linear(feats, w, "score_head")[:, 0], feats
 
 
@@ -111,9 +134,12 @@ def edge_graph_ids(edge_index, ptr) -> torch.Tensor:
 
 
 def retriever_forward(w: Dict[str, torch.Tensor], batch, *, num_rounds: int, num_reverse_rounds: int,
-                      direction_mode: str = "bidirectional", edge_bias=None) -> Dict[str, Optional[torch.Tensor]]:
-    """Eval-mode forward on a flat batch (attributes as evi_rag_amd.synthetic.SyntheticBatch: numpy arrays or tensors; the
+                      direction_mode: str = "bidirectional", edge_bias=None, dropout_mul=None) -> Dict[str, Optional[torch.Tensor]]:
+    """Forward on a flat batch (attributes as evi_rag_amd.synthetic.SyntheticBatch: numpy arrays or tensors; the
     relation rows either as `edge_embeddings` [E, D] or as `relation_embedding_table` [R, D] gathered by `edge_attr`).
+    dropout_mul: None (eval mode) or the [2, E, H] multipliers (0 or 1 / (1 - p)) of the training-mode dropout on state_net's
+    GELU output, [0] for the forward and [1] for the backward scoring direction (oracle/scorer.py: score_edges); a
+    single-direction mode reads its own slice only.
     Returns logits, logits_fwd, logits_bwd, edge_embeddings, node_struct, query_ids; differentiable w.r.t. `w`."""
     ei = _cpu(batch.edge_index).to(torch.int64)
     head, tail = ei[0], ei[1]
@@ -132,9 +158,11 @@ def retriever_forward(w: Dict[str, torch.Tensor], batch, *, num_rounds: int, num
     ns = node_structure_features(batch.topic_one_hot, ei, num_rounds, num_reverse_rounds)
     lf = ff = lb = fb = None
     if direction_mode in ("forward", "bidirectional"):
-        lf, ff = _score_edges(w, query_repr, head_repr, relation_repr, tail_repr, torch.cat([ns[head], ns[tail]], dim=-1))
+        lf, ff = _score_edges(w, query_repr, head_repr, relation_repr, tail_repr, torch.cat([ns[head], ns[tail]], dim=-1),
+                              None if dropout_mul is None else dropout_mul[0])
     if direction_mode in ("backward", "bidirectional"):
-        lb, fb = _score_edges(w, query_repr, tail_repr, relation_repr, head_repr, torch.cat([ns[tail], ns[head]], dim=-1))
+        lb, fb = _score_edges(w, query_repr, tail_repr, relation_repr, head_repr, torch.cat([ns[tail], ns[head]], dim=-1),
+                              None if dropout_mul is None else dropout_mul[1])
     if edge_bias is not None:  # added to both directional logits before the combine
         eb = _f64(edge_bias).reshape(-1)
         lf = None if lf is None else lf + eb

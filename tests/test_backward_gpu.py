@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from evi_rag_amd import synthetic
+from tests.scorer_f64 import _dropout_multipliers
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -184,21 +185,6 @@ def test_replayed_forward_intermediates_give_the_recomputing_backwards_bits(dev,
         assert torch.equal(grads[True][n], grads[False][n]), n
     assert float(grads[True]["state_net.0.weight"].abs().max()) > 0
     assert bool(sized) == edge_rows_only
-
-
-def _dropout_multipliers(seed, E, H, p):
-    """The kernel's dropout mask restated with numpy integers (csrc/scorer.hip: dropout_mul4): [2, E, H] multipliers."""
-    thr = min(int(round(p * 65536.0)), 65535)
-    scale = np.float32(65536.0 / (65536 - thr))
-    rows = np.arange(2 * E, dtype=np.uint64)[:, None]
-    quads = np.arange(H // 4, dtype=np.uint64)[None, :]
-    with np.errstate(over="ignore"):
-        z = np.uint64(seed) + np.uint64(0x9E3779B97F4A7C15) * (rows * np.uint64(H // 4) + quads + np.uint64(1))
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    u = np.stack([(z >> np.uint64(16 * c)) & np.uint64(0xFFFF) for c in range(4)], axis=-1).reshape(2 * E, H)
-    return np.where(u >= thr, scale, np.float32(0)).astype(np.float32).reshape(2, E, H)
 
 
 def test_training_mode_dropout_and_hide_and_seek(dev, monkeypatch):

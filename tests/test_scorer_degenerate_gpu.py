@@ -350,7 +350,7 @@ def _compare_outputs(tag, out, ref):
     return max(errs.values())
 
 
-def _compare(tag, gemm, out, model, ref):
+def _compare(tag, gemm, out, model, ref, label="degenerate"):
     """Outputs and all 25 gradients of the product against the float64 reference (the rules above KAPPA); prints the worst
     figures, then asserts."""
     ratios, one_element, must_be_zero, cancelled = {}, {}, {}, {}
@@ -370,11 +370,11 @@ def _compare(tag, gemm, out, model, ref):
             ratios[name] = err / max(scale, 1e-6)
     assert len(ratios) + len(one_element) + len(must_be_zero) + len(cancelled) == 25
     top = max(ratios, key=ratios.get)
-    print(f"\n[degenerate] {tag} gemm={gemm}: grad {ratios[top]:.1e} ({top})"
+    print(f"\n[{label}] {tag} gemm={gemm}: grad {ratios[top]:.1e} ({top})"
           + "".join(f"  {n}: {r:.1e} at kappa {k:.0f}" for n, (r, k) in one_element.items())
           + "".join(f"  {n} cancelled: {r:.1e} of its bound" for n, r in cancelled.items()))
     worst_out = _compare_outputs(tag, out, ref)
-    print(f"[degenerate] {tag} gemm={gemm}: out {worst_out:.1e}")
+    print(f"[{label}] {tag} gemm={gemm}: out {worst_out:.1e}")
     for name, got_max in must_be_zero.items():
         assert got_max == 0.0, (tag, name, "no term in float64", got_max)
     for name, r in cancelled.items():
@@ -386,7 +386,7 @@ def _compare(tag, gemm, out, model, ref):
 
 
 def _run_gvec(dev, tag, gemm, monkeypatch, b, D, H, *, rounds=(2, 2), mode="bidirectional", table_form=False, keep=True,
-              ref_key=None, **model_kw):
+              ref_key=None, label="degenerate", **model_kw):
     """The product's eval-mode graph on batch b: d (logits . gvec) / d parameter, against the float64 model."""
     _set_gemm(monkeypatch, gemm)
     ref = _reference(ref_key or (tag, D, H, rounds, mode), b, D, H, rounds, mode)
@@ -398,7 +398,7 @@ def _run_gvec(dev, tag, gemm, monkeypatch, b, D, H, *, rounds=(2, 2), mode="bidi
     (out.logits * torch.from_numpy(b.gvec).to(dev)).sum().backward()
     torch.cuda.synchronize()
     assert np.array_equal(out.query_ids.cpu().numpy(), np.repeat(np.arange(b.num_graphs), np.diff(b.edge_ptr)))
-    _compare(tag, gemm, out, model, ref)
+    _compare(tag, gemm, out, model, ref, label=label)
     return model
 
 

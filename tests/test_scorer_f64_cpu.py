@@ -17,6 +17,9 @@ The float64 loss is pinned to oracle/loss.py (f32 arithmetic, closed-form d tota
 total within 2e-6 relative, gradient within 1e-5 of its max — both f32 rounding of the oracle (measured at most 1.2e-07 / 2.0e-07).
 `edge_bias` (no golden carries one) is pinned to the f32 oracle's handling of it in the bidirectional mode, same 2e-6 bar
 (measured 3.9e-07 on the logits), and to its definition in the single-direction modes: the logits move by the bias.
+The training-mode dropout form (`dropout_mul`, no golden carries one either) is pinned to the f32 oracle given the same mask —
+the kernel's own, p = 0.25 — on the toy golden at the same 2e-6 bar (measured 4.3e-07 on the edge embeddings, 1.5e-07 on the logits), and a mask of ones is
+the eval-mode result bit for bit.
 """
 import os
 import types
@@ -113,3 +116,41 @@ def test_float64_edge_bias_moves_both_directional_logits_before_the_combine():
         moved = f64.retriever_forward(w, batch, edge_bias=bias, **kw)
         assert torch.allclose(moved["logits"], plain["logits"] + torch.from_numpy(bias).double(), rtol=0, atol=1e-12)
         assert torch.equal(moved["edge_embeddings"], plain["edge_embeddings"])
+
+
+def test_float64_dropout_form_is_the_oracle_given_the_same_mask():
+    """`retriever_forward(..., dropout_mul=)`: the [2, E, H] multipliers scale the GELU output of state_net per direction, where
+    oracle/scorer.py: score_edges applies them.  The mask is the kernel's (p = 0.25, a quarter of the entries zero, the rest
+    4 / 3); all four outputs against the f32 oracle given the same mask, at the eval-mode bar.  A mask of ones changes nothing,
+    exactly; the real mask does."""
+    z, batch, w, kw = _load("retriever_toy")
+    E, H = int(z["logits"].size), int(z["H"])
+    mul = f64._dropout_multipliers(0x1234567890ABCDEF, E, H, 0.25)
+    assert mul.shape == (2, E, H) and set(np.unique(mul).tolist()) == {0.0, float(np.float32(4.0 / 3.0))}
+    assert abs(float((mul > 0).mean()) - 0.75) < 0.02 and not np.array_equal(mul[0], mul[1])
+    got = f64.retriever_forward(w, batch, dropout_mul=mul, **kw)
+    want = oscorer.retriever_forward({k[2:]: z[k] for k in z.files if k.startswith("w_")}, batch, dropout_mul=mul, **kw)
+    keys = ("logits", "logits_fwd", "logits_bwd", "edge_embeddings")
+    worst = {k: float(np.abs(got[k].detach().numpy() - want[k]).max()) for k in keys}
+    print("\ndropout_mul vs the f32 oracle: " + "  ".join(f"{k} {v:.1e}" for k, v in worst.items()))
+    assert max(worst.values()) <= OUT_ATOL, worst
+    plain = f64.retriever_forward(w, batch, **kw)
+    ones = f64.retriever_forward(w, batch, dropout_mul=np.ones((2, E, H), np.float32), **kw)
+    for k in keys:
+        assert torch.equal(ones[k], plain[k]), k
+    assert float((got["logits"] - plain["logits"]).detach().abs().max()) > 1e-3
+    # a single-direction model reads the slice of its own direction: [0] forward, [1] backward
+    for name, used, other in (("retriever_fwd", 0, 1), ("retriever_bwd", 1, 0)):
+        z, batch, w, kw = _load(name)
+        E, H = int(z["logits"].size), int(z["H"])
+        mul = f64._dropout_multipliers(77, E, H, 0.25)
+        got = f64.retriever_forward(w, batch, dropout_mul=mul, **kw)
+        want = oscorer.retriever_forward({k[2:]: z[k] for k in z.files if k.startswith("w_")}, batch, dropout_mul=mul, **kw)
+        assert float(np.abs(got["logits"].detach().numpy() - want["logits"]).max()) <= OUT_ATOL
+        changed = mul.copy()
+        changed[other] = 1.0
+        again = f64.retriever_forward(w, batch, dropout_mul=changed, **kw)
+        assert torch.equal(again["logits"], got["logits"]) and torch.equal(again["edge_embeddings"], got["edge_embeddings"])
+        changed = mul.copy()
+        changed[used] = 1.0
+        assert not torch.equal(f64.retriever_forward(w, batch, dropout_mul=changed, **kw)["logits"], got["logits"])
