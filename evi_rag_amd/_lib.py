@@ -113,6 +113,8 @@ _SIGNATURES = {
                                                    c_size_t, _P]),
     "evi_cosine_topk_gemm_f16": (c_int, [_P, c_int, _P, c_int64, c_int, _P, c_int, c_int64, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "evi_cosine_topk_gemm_fp8": (c_int, [_P, c_int, _P, c_int64, c_int, _P, c_int, c_int64, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "evi_cosine_topk_gemm_filtered": (c_int, [_P, c_int, _P, c_int, c_int64, c_int, _P, _P, _P, c_int, c_int64, c_int, _P, _P, _P, _P,
+                                              _P, c_size_t, _P]),
     "evi_cosine_topk_gemm_fp8_selection": (c_int, [_P, c_int, _P, c_int64, c_int, _P, c_int, _P, _P, c_size_t, _P]),
     "evi_topk_merge": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "evi_topk_packed_bytes": (c_size_t, [c_int, c_int]),

@@ -88,6 +88,10 @@ struct GemmFilter {
     int32_t* cand_cnt;       // [N * cnt_stride]
     int32_t* status;         // |= 2 when a list is full
     int cap, cnt_stride;
+    // row filter (launch_gemm_bf16x3_filter takes the filtered epilogue when both are set): row m is appended to column n's
+    // list only if row_labels[row0 + m] < 32 and bit row_labels[row0 + m] of query_allow[n] is set
+    const uint8_t* row_labels = nullptr;    // [>= row0 + M]
+    const uint32_t* query_allow = nullptr;  // [N]
 };
 // W [N, K] -> bf16 hi / lo planes in wsplit (once); then C = A W^T with the planes, or the filter epilogue.
 // gridDim.y-batched K-slices of one product (split-K); count == 0: a plain GEMM

@@ -1034,11 +1034,16 @@ __global__ void k_gt_init(float* tau, int32_t* cnt, int Q, int32_t* status) {
 }
 
 // scores [rows, Q] (row-major) of slab rows [row0, row0 + rows): append (score * row_scale, row) to the list of
-// every query whose current threshold it reaches
+// every query whose current threshold it reaches.  FILTER: only where the row is visible to the query (row_labels[row] < 32
+// and bit row_labels[row] of query_allow[query] set) — a hidden pair is never appended, NaN score or not; FILTER == false
+// is the unfiltered kernel and reads neither array.
+template <bool FILTER>
 __global__ __launch_bounds__(256) void k_gt_filter(const float* __restrict__ scores, int64_t rows, int Q, int64_t row0,
                                                    const float* __restrict__ row_scale, const float* __restrict__ tau,
                                                    float* __restrict__ cand_score, int32_t* __restrict__ cand_id,
-                                                   int32_t* __restrict__ cand_cnt, int32_t* __restrict__ status) {
+                                                   int32_t* __restrict__ cand_cnt, int32_t* __restrict__ status,
+                                                   const uint8_t* __restrict__ row_labels,
+                                                   const uint32_t* __restrict__ query_allow) {
     const int64_t total = rows * Q;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = i / Q;
@@ -1046,6 +1051,10 @@ __global__ __launch_bounds__(256) void k_gt_filter(const float* __restrict__ sco
         float s = scores[i];
         if (row_scale) s *= row_scale[row0 + r];
         if (s >= tau[qi] || s != s) {
+            if (FILTER) {
+                const uint32_t label = row_labels[row0 + r];
+                if (label >= 32u || ((query_allow[qi] >> label) & 1u) == 0u) continue;
+            }
             const int32_t pos = atomicAdd(&cand_cnt[qi * kCntStride], 1);
             if (pos < kGemmTopkCap) {
                 cand_score[(int64_t)qi * kGemmTopkCap + pos] = s;
@@ -1088,7 +1097,7 @@ __global__ void k_gt_gap(const float* __restrict__ q, int Q, int D, const float*
             const float* s = cand_score + (int64_t)qi * kGemmTopkCap;
             const bool norm_ok = !q_norm_guard || (ss >= 0.0625f && ss <= 16.0f);
             if (gap_fails(s[k - 1] - s[kk - 1], eps, ss) || !norm_ok) atomicOr(status, 1);
-        }  // m < kk: every row of the index is in the list
+        }  // m < kk: every row of the index (with a row filter: every row visible to this query) is in the list
     }
 }
 
@@ -1357,9 +1366,15 @@ __global__ void k_gt_scale_rows(float* __restrict__ scores, int64_t rows, int Q,
         scores[i] *= row_scale[i / Q];
 }
 
+// row_labels / query_allow (both or neither): the row filter of the scan.  A hidden (query, row) pair is never appended
+// to a list, so the lists, the thresholds, the gap test and the rescore speak of the rows visible to each query only — the
+// compacted index.  A query with fewer than kk visible rows keeps tau = -inf to the end (tau is raised only on a list of kk
+// real entries), every slab appends all of its visible rows, and the final writer pads with (-inf, -1).
 static int cosine_topk_gemm_impl(const float* q, int Q, const void* idx, IndexKind kind, int products, const void* shadow, int64_t N,
                                  int D, const float* row_scale, int k, int64_t row_id_base, float* out_score,
-                                 int64_t* out_index, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+                                 int64_t* out_index, int32_t* status, void* workspace, size_t workspace_bytes, void* stream,
+                                 const uint8_t* row_labels = nullptr, const uint32_t* query_allow = nullptr) {
+    EVI_REQUIRE((row_labels == nullptr) == (query_allow == nullptr), "evi_cosine_topk_gemm: row_labels and query_allow go together");
     EVI_REQUIRE(products == 1 || products == 3, "evi_cosine_topk_gemm: products must be 3 (split-bf16) or 1 (plain bf16), got %d",
                 products);
     const int single = products == 1;
@@ -1399,6 +1414,14 @@ static int cosine_topk_gemm_impl(const float* q, int Q, const void* idx, IndexKi
     EVI_LAUNCH_CHECK();
     int rc = gt_query_planes(kind, q, Q, D, base + L.wsplit, st);
     if (rc != EVI_OK) return rc;
+    // Slab growth.  Unfiltered, a slab of g times the rows seen so far appends about g kk rows to a list of kk.  A filter of
+    // independent labels thins the slab and the rows behind tau alike, so the expectation stands; while a query has seen
+    // fewer than kk visible rows its tau is still -inf and it takes every visible row of the slab, which is fewer than g kk.
+    // Either way the list needs (1 + g) kk slots: the filtered call lowers g until that is inside 8/9 of the capacity (kk up
+    // to 1618 keeps 8; kk = 2048 gets 6), since its overflow costs a whole filtered scan.
+    int growth = kGemmGrowth;
+    if (row_labels)
+        while (growth > 2 && (int64_t)kk * (1 + growth) * 9 > (int64_t)kGemmTopkCap * 8) --growth;
     int64_t begin = 0, seg = N < kGemmFirstRows ? N : kGemmFirstRows;
     while (begin < N) {
         const int64_t rows = (N - begin) < seg ? (N - begin) : seg;
@@ -1409,12 +1432,16 @@ static int cosine_topk_gemm_impl(const float* q, int Q, const void* idx, IndexKi
             if (rc != EVI_OK) return rc;
             int64_t blocks = (rows * Q + 255) / 256;
             if (blocks > 8192) blocks = 8192;
-            hipLaunchKernelGGL(k_gt_filter, dim3((unsigned)blocks), dim3(256), 0, st, scores, rows, Q, begin, row_scale, tau,
-                               cs, ci, cnt, status);
+            if (row_labels)
+                hipLaunchKernelGGL(k_gt_filter<true>, dim3((unsigned)blocks), dim3(256), 0, st, scores, rows, Q, begin, row_scale,
+                                   tau, cs, ci, cnt, status, row_labels, query_allow);
+            else
+                hipLaunchKernelGGL(k_gt_filter<false>, dim3((unsigned)blocks), dim3(256), 0, st, scores, rows, Q, begin, row_scale,
+                                   tau, cs, ci, cnt, status, (const uint8_t*)nullptr, (const uint32_t*)nullptr);
         } else {
             // later slabs: scores ~ idx[begin + r] . q[i] never leave the registers of the GEMM — its epilogue
             // compares them with tau and appends the few survivors
-            const GemmFilter flt{tau, row_scale, begin, cs, ci, cnt, status, kGemmTopkCap, kCntStride};
+            const GemmFilter flt{tau, row_scale, begin, cs, ci, cnt, status, kGemmTopkCap, kCntStride, row_labels, query_allow};
             rc = launch_gemm_bf16x3_filter(slab, a_kind, single, rows, D, D, base + L.wsplit, Q, flt, st);
             if (rc != EVI_OK) return rc;
         }
@@ -1424,7 +1451,7 @@ static int cosine_topk_gemm_impl(const float* q, int Q, const void* idx, IndexKi
                            (const int32_t*)nullptr);
         EVI_LAUNCH_CHECK();
         begin += rows;
-        int64_t next = begin * kGemmGrowth;
+        int64_t next = begin * growth;
         seg = next < L.slab ? next : L.slab;
     }
     hipLaunchKernelGGL(k_gt_gap, dim3(Q), dim3(64), 0, st, q, Q, D, cs, cnt, k, kk,
@@ -1463,6 +1490,21 @@ extern "C" int evi_cosine_topk_gemm_fp8(const float* q, int Q, const void* idx_f
                                         int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
     return cosine_topk_gemm_impl(q, Q, idx_fp8, native_mfma ? kIdxFp8Mfma : kIdxFp8Widen, 3, nullptr, N, D, row_scale, k,
                                  row_id_base, out_score, out_index, status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int evi_cosine_topk_gemm_filtered(const float* q, int Q, const void* idx, int kind, int64_t N, int D,
+                                             const float* row_scale, const uint8_t* row_labels, const uint32_t* query_allow,
+                                             int k, int64_t row_id_base, int products, const void* shadow_bf16, float* out_score,
+                                             int64_t* out_index, int32_t* status, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
+    EVI_REQUIRE(kind >= 0 && kind <= 3, "evi_cosine_topk_gemm_filtered: kind must be 0 (f32), 1 (f16), 2 (e4m3 widened) or 3 (e4m3 "
+                "native), got %d", kind);
+    EVI_REQUIRE(row_labels && query_allow, "evi_cosine_topk_gemm_filtered: null row_labels / query_allow");
+    EVI_REQUIRE(kind < 2 || (products == 3 && !shadow_bf16),
+                "evi_cosine_topk_gemm_filtered: an e4m3 index has one selection precision (products = 3) and no bf16 shadow");
+    static const IndexKind kinds[4] = {kIdxF32, kIdxF16, kIdxFp8Widen, kIdxFp8Mfma};
+    return cosine_topk_gemm_impl(q, Q, idx, kinds[kind], products, shadow_bf16, N, D, row_scale, k, row_id_base, out_score,
+                                 out_index, status, workspace, workspace_bytes, stream, row_labels, query_allow);
 }
 
 extern "C" int evi_cosine_topk_gemm_fp8_selection(const float* q, int Q, const void* idx_fp8, int64_t N, int D,

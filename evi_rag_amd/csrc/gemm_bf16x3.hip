@@ -403,12 +403,16 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
       }
     }
 
-    if (ACT == 3) {  // threshold filter instead of a store: survivors are rare after the first slab
+    // ACT == 4: the same with a row filter.  The score is compared with tau FIRST and the row's label byte is read only for
+    // a score that passes, so in steady state (survivors are rare) the filter adds no memory traffic; the allow word is read
+    // once per column beside tau.  A hidden pair is never appended, NaN score or not, and no label of a row m >= M is read.
+    if (ACT == 3 || ACT == 4) {  // threshold filter instead of a store: survivors are rare after the first slab
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int n = n0 + wn * 64 + j * 32 + fr;
             if (n >= N) continue;
             const float t = flt.tau[n];
+            const uint32_t allow = ACT == 4 ? flt.query_allow[n] : 0u;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -418,6 +422,10 @@ __global__ __launch_bounds__(kXThreads) void k_gemm_nt_bf16x3(
                     float sc = acc[i][j][r];
                     if (flt.row_scale) sc *= flt.row_scale[flt.row0 + m];
                     if (sc >= t || sc != sc) {
+                        if (ACT == 4) {
+                            const uint32_t label = flt.row_labels[flt.row0 + m];
+                            if (label >= 32u || ((allow >> label) & 1u) == 0u) continue;
+                        }
                         const int32_t pos = atomicAdd(&flt.cand_cnt[n * flt.cnt_stride], 1);
                         if (pos < flt.cap) {
                             flt.cand_score[(int64_t)n * flt.cap + pos] = sc;
@@ -509,14 +517,21 @@ int launch_gemm_bf16_presplit(const void* A, int a_f16, int single, int64_t M, i
 int launch_gemm_bf16x3_filter(const void* A, int a_f16, int single, int64_t M, int K, int64_t lda, const void* wsplit, int N,
                               const GemmFilter& flt, hipStream_t st) {
     if (M == 0 || N == 0) return EVI_OK;
+    const bool labelled = flt.row_labels != nullptr;  // the row-filter epilogue (ACT 4) instead of the plain threshold one (3)
+    if (labelled != (flt.query_allow != nullptr)) return fail(EVI_ERR_INVALID, "gemm filter: row_labels and query_allow go together");
     const int Kp = (K + XK - 1) / XK * XK;
     const __bf16* hi = static_cast<const __bf16*>(wsplit);
     const __bf16* lo = reinterpret_cast<const __bf16*>(static_cast<const char*>(wsplit) + align_up((size_t)N * Kp * 2, 256));
     const dim3 grid((unsigned)(((M + XM - 1) / XM) * ((N + XN - 1) / XN)));
     const int tok = timing_begin(kTimeGemm, st);
-#define EVI_LAUNCH_FL(AHV, P1V)                                                                                          \
-    hipLaunchKernelGGL((k_gemm_nt_bf16x3<3, AHV, P1V>), grid, dim3(kXThreads), 0, st, static_cast<const float*>(A), M, K, lda, \
+#define EVI_LAUNCH_FA(ACTV, AHV, P1V)                                                                                    \
+    hipLaunchKernelGGL((k_gemm_nt_bf16x3<ACTV, AHV, P1V>), grid, dim3(kXThreads), 0, st, static_cast<const float*>(A), M, K, lda, \
                        hi, lo, N, Kp, static_cast<const float*>(nullptr), static_cast<float*>(nullptr), (int64_t)0, flt, GemmBatch{})
+#define EVI_LAUNCH_FL(AHV, P1V)                 \
+    do {                                        \
+        if (labelled) EVI_LAUNCH_FA(4, AHV, P1V); \
+        else EVI_LAUNCH_FA(3, AHV, P1V);        \
+    } while (0)
     if (a_f16 == 3) EVI_LAUNCH_FL(3, 0);
     else if (a_f16 == 2) EVI_LAUNCH_FL(2, 1);
     else if (a_f16 && single) EVI_LAUNCH_FL(1, 1);
@@ -524,6 +539,7 @@ int launch_gemm_bf16x3_filter(const void* A, int a_f16, int single, int64_t M, i
     else if (single) EVI_LAUNCH_FL(0, 1);
     else EVI_LAUNCH_FL(0, 0);
 #undef EVI_LAUNCH_FL
+#undef EVI_LAUNCH_FA
     timing_end(tok, st);
     EVI_LAUNCH_CHECK();
     return EVI_OK;

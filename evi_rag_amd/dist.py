@@ -37,12 +37,15 @@ def shard_graphs(num_graphs: int, rank: int, world_size: int) -> List[int]:
 def _default_local_topk(queries, shard, k, row_id_base, row_scale=None, method="scan", fp8_mfma=False, **row_filter):
     from . import ops
 
+    if method == "gemm" and row_filter:  # ops.cosine_topk(method="gemm") takes no filter: the filtered many-query pass by name
+        return ops.cosine_topk_gemm(queries, shard, k, row_id_base=row_id_base, row_scale=row_scale, fp8_mfma=fp8_mfma, **row_filter)
     return ops.cosine_topk(queries, shard, k, row_id_base=row_id_base, row_scale=row_scale, method=method, fp8_mfma=fp8_mfma,
                            **row_filter)
 
 
 def _local_scan(self: "ShardedIndex", queries, k, out, workspace, lane: int = 0, row_filter: Optional[dict] = None):
-    """The shard's exact top-k into `out` on the current stream, without a read-back.  method "two_stage": the f16
+    """The shard's exact top-k into `out` on the current stream — without a read-back, except for method "gemm", whose pass
+    (ops.cosine_topk_gemm, filtered or not) reads its proof flag back once per batch.  method "two_stage": the f16
     shadow is scanned and the f32 rows re-score (ops.cosine_topk_two_stage) with the DEVICE-SIDE fallback: a batch whose
     exactness proof fails is re-done by the gated f32 scan before the record leaves the device, so what a rank
     contributes to the exchange is always exact and the ranks need no agreement.  self.two_stage_status only records
@@ -55,6 +58,9 @@ def _local_scan(self: "ShardedIndex", queries, k, out, workspace, lane: int = 0,
         return ops.cosine_topk_two_stage(queries, self.shard, self.shadow, k, row_id_base=self.row_begin, out=out,
                                          status=self.two_stage_status, fallback="device",
                                          workspace=self._two_stage_workspace(queries, k, lane), **flt)
+    if self.method == "gemm" and flt:  # the filtered many-query pass (its fallback is the filtered scan, into the same record)
+        return ops.cosine_topk_gemm(queries, self.shard, k, row_id_base=self.row_begin, row_scale=self.row_scale, out=out,
+                                    fp8_mfma=self.fp8_mfma, **flt)
     return ops.cosine_topk(queries, self.shard, k, row_id_base=self.row_begin, row_scale=self.row_scale,
                            workspace=workspace, out=out, method=self.method, fp8_mfma=self.fp8_mfma, **flt)
 

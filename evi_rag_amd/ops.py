@@ -251,8 +251,9 @@ def cosine_topk(
       The result is the exact top-k of the visible rows — the ids and the score bits of cosine_topk on the compacted
       index, mapped back — with (-inf, -1) past the number of visible rows; a hidden row never appears, NaN score or not.
       With a filter "auto" takes the two-stage scan when the f16 shadow is resident and the scan otherwise, never the
-      GEMM-shaped pass, and method="gemm" raises ValueError: a filtered many-query pass is not part of this library yet,
-      so Q >= 96 with a filter pays one scan of the index per 32 queries."""
+      GEMM-shaped pass, and method="gemm" raises ValueError, so here Q >= 96 with a filter pays one scan of the index per
+      32 queries.  The filtered many-query pass is called by name: cosine_topk_gemm(..., row_labels=..., query_allow=...)
+      or row_mask=... (same result, one pass over the index)."""
     if method not in ("scan", "gemm", "auto"):
         raise ValueError(f"method must be 'scan', 'gemm' or 'auto', got {method!r}")
     if row_mask is not None or row_labels is not None or query_allow is not None:
@@ -305,8 +306,8 @@ def _cosine_topk_filtered(queries, index, k, row_scale, row_id_base, workspace, 
                           query_allow):
     """cosine_topk with a row filter (see there): the two-stage scan or the scan, through the filtered entry points."""
     if method == "gemm":
-        raise ValueError("method='gemm' takes no row filter: the GEMM-shaped many-query pass has no filtered form "
-                         "(use 'auto' or 'scan')")
+        raise ValueError("method='gemm' takes no row filter here: call cosine_topk_gemm(..., row_labels=..., query_allow=...) "
+                         "for the filtered many-query pass (or use 'auto' or 'scan')")
     if queries.dim() != 2 or index.dim() != 2:
         raise ValueError("queries and index must be 2D")
     _check_topk_filter(row_mask, row_labels, query_allow, index.size(0), queries.size(0))
@@ -430,7 +431,9 @@ def cosine_topk_gemm(queries: torch.Tensor, index: torch.Tensor, k: int, *, row_
                      row_id_base: int = 0, fallback: bool = True,
                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                      products: Optional[int] = None, shadow: Optional[torch.Tensor] = None,
-                     check_norms: bool = True, fp8_mfma: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                     check_norms: bool = True, fp8_mfma: Optional[bool] = None,
+                     row_mask: Optional[torch.Tensor] = None, row_labels: Optional[torch.Tensor] = None,
+                     query_allow: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """cosine_topk for many queries at once (see evi_cosine_topk_gemm): one split-bf16 GEMM pass over the index
     selects candidates, the scan's arithmetic re-scores them; the result equals cosine_topk bit for bit.  Reads the
     proof flag back (one synchronisation); when the proof fails (heavy score ties, adversarial row order) the scan
@@ -440,22 +443,43 @@ def cosine_topk_gemm(queries: torch.Tensor, index: torch.Tensor, k: int, *, row_
     evi_cosine_topk_gemm_fp8: the stored bytes are streamed once and widened to bf16 exactly inside the GEMM, two bf16
     products.  fp8_mfma has the meaning and default (None = True) it has in cosine_topk: the result equals, bit for
     bit, the scan of THAT variant, and the scan fallback runs that variant.  There is one selection precision, so
-    `products` must stay None, and no `shadow`.  The norm check allows stored rows (codes x scale) up to 1 + 2^-4."""
+    `products` must stay None, and no `shadow`.  The norm check allows stored rows (codes x scale) up to 1 + 2^-4.
+    Row filter (row_mask, or row_labels + query_allow: the keywords and rules of cosine_topk, all index kinds): a hidden
+    (query, row) pair never enters a candidate list, so the pass selects, proves and re-scores among the rows visible to
+    each query; the result equals the filtered scan — cosine_topk on the compacted index, ids mapped back — bit for bit,
+    with (-inf, -1) past the number of visible rows.  The label byte is read only for a score that already passes the
+    query's threshold.  Every fallback (norm check, failed proof, overflow) runs the filtered scan.  Meant for interleaved
+    labels (tombstones, non-text rows, split membership): labels that hide a long run of rows in front of visible ones
+    overflow a candidate list (status 2) and pay one pass plus the scan (the other selection precision is not tried: it
+    would overflow alike); a contiguous scope is a slice (index[a:b] with row_id_base=a) and needs no filter.
+    `last_status` holds the status of the last pass run (0 proven, 1 gap test failed, 2 a list overflowed), `last_products`
+    the selection precision that proved the result, 0 when the scan produced it."""
     if products not in (None, 1, 3):
         raise ValueError(f"products must be None, 1 or 3, got {products}")
+    filt = {"row_mask": row_mask, "row_labels": row_labels, "query_allow": query_allow}
+    filtered = any(t is not None for t in filt.values())
+    if filtered:
+        if queries.dim() != 2 or index.dim() != 2:
+            raise ValueError("queries and index must be 2D")
+        _check_topk_filter(row_mask, row_labels, query_allow, index.size(0), queries.size(0))
     if index.dtype == torch.uint8:
-        return _cosine_topk_gemm_fp8(queries, index, k, row_scale, row_id_base, fallback, out, products, shadow, check_norms, fp8_mfma)
+        return _cosine_topk_gemm_fp8(queries, index, k, row_scale, row_id_base, fallback, out, products, shadow, check_norms, fp8_mfma,
+                                     filt if filtered else None)
     if fp8_mfma:
         raise ValueError("fp8_mfma goes with an e4m3 (uint8) index")
     if shadow is not None:
         if index.dtype != torch.float32 or shadow.dtype != torch.bfloat16 or shadow.shape != index.shape or not shadow.is_contiguous():
             raise ValueError("shadow must be the contiguous bfloat16 copy of an f32 index (index_shadow_bf16)")
-    dev = _require_gpu(queries, index, row_scale)
+    dev = _require_gpu(queries, index, row_scale, row_mask, row_labels, query_allow)
     q, x, row_scale = _topk_operands(queries, index, row_scale)  # f16 storage: evi_cosine_topk_gemm_f16
     Q, D = q.shape
     N = x.shape[0]
+
+    def scan():  # with the same filter keywords (all None: the unfiltered scan)
+        return cosine_topk(q, x, k, row_scale=row_scale, row_id_base=row_id_base, out=out, method="scan", **filt)
+
     if Q == 0 or N == 0:
-        return cosine_topk(q, x, k, row_scale=row_scale, row_id_base=row_id_base, out=out, method="scan")
+        return scan()
     # the proof's error bound is kApproxEps * |q| * |row|, with |row| <= 1 built in: an index of longer rows would pass
     # the gap test with true top-k rows discarded.  Verified once per index (cached); such an index goes to the scan.
     if check_norms and not rows_are_unit_norm(x, row_scale):
@@ -463,12 +487,14 @@ def cosine_topk_gemm(queries: torch.Tensor, index: torch.Tensor, k: int, *, row_
             raise ValueError("cosine_topk_gemm needs rows of norm <= 1 (normalize_embeddings, or row_scale = row_inv_norm): "
                              "its exactness proof assumes them")
         cosine_topk_gemm.last_products = 0
-        return cosine_topk(q, x, k, row_scale=row_scale, row_id_base=row_id_base, out=out, method="scan")
+        return scan()
     lib = _lib.load()
     ws = _workspace(dev, "cosine_topk_gemm", int(lib.evi_cosine_topk_gemm_workspace_bytes(Q, N, D, int(k))))
     out_score, out_index = _topk_out(out, Q, k, dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    fn = lib.evi_cosine_topk_gemm_f16 if x.dtype == torch.float16 else lib.evi_cosine_topk_gemm
+    f16 = x.dtype == torch.float16
+    if filtered:
+        labels, allow = _topk_filter_operands(row_mask, row_labels, query_allow, Q, dev)
     # The single-product (plain bf16) selection keeps max(1024, k) reserve rows per query and needs the k-th and the last kept
     # score 2 x 4.2e-3 |q| apart: the rows inside that band grow with N (about 390 of the 1024 at 2^23 rows of an exchangeable
     # index, i.e. more than the reserve beyond ~2 x 10^7 rows) — there the attempt only costs a wasted pass (measured at 10^8
@@ -476,36 +502,44 @@ def cosine_topk_gemm(queries: torch.Tensor, index: torch.Tensor, k: int, *, row_
     plan = [products] if products is not None else ([1, 3] if (k <= 1024 and N <= (1 << 24)) else [3])
     st = -1
     for prod in plan:
-        if x.dtype == torch.float16:
-            args = (int(prod),)
+        shadow_ptr = _ptr(shadow) if (shadow is not None and prod == 1) else None
+        tail = (_ptr(out_score), _ptr(out_index), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
+        if filtered:
+            rc = lib.evi_cosine_topk_gemm_filtered(_ptr(q), Q, _ptr(x), 1 if f16 else 0, N, D, _ptr(row_scale), _ptr(labels), _ptr(allow),
+                                                   int(k), int(row_id_base), int(prod), shadow_ptr, *tail)
+        elif f16:
+            rc = lib.evi_cosine_topk_gemm_f16(_ptr(q), Q, _ptr(x), N, D, _ptr(row_scale), int(k), int(row_id_base), int(prod), *tail)
         else:
-            args = (int(prod), _ptr(shadow) if (shadow is not None and prod == 1) else None)
-        _lib.check(fn(_ptr(q), Q, _ptr(x), N, D, _ptr(row_scale), int(k), int(row_id_base), *args, _ptr(out_score),
-                      _ptr(out_index), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
-        st = int(status.item())
+            rc = lib.evi_cosine_topk_gemm(_ptr(q), Q, _ptr(x), N, D, _ptr(row_scale), int(k), int(row_id_base), int(prod), shadow_ptr,
+                                          *tail)
+        _lib.check(rc)
+        st = cosine_topk_gemm.last_status = int(status.item())  # of the last pass run, filtered or not
         if st == 0:
             cosine_topk_gemm.last_products = prod  # which selection precision proved the result (introspection / bench)
             break
+        if filtered and st & 2:
+            break  # a list overflowed: with a filter that is the label layout, which a finer selection precision does not change
     if st != 0:
         cosine_topk_gemm.last_products = 0  # the scan produced the result
         if not fallback:
             raise RuntimeError(f"evi_cosine_topk_gemm could not prove exactness (status {st}): run cosine_topk")
-        return cosine_topk(q, x, k, row_scale=row_scale, row_id_base=row_id_base, out=out, method="scan")
+        return scan()
     return out_score, out_index
 
 
 cosine_topk_gemm.last_products = None
 
 
-def _cosine_topk_gemm_fp8(queries, index, k, row_scale, row_id_base, fallback, out, products, shadow, check_norms, fp8_mfma):
-    """cosine_topk_gemm over an e4m3 index (see there)."""
+def _cosine_topk_gemm_fp8(queries, index, k, row_scale, row_id_base, fallback, out, products, shadow, check_norms, fp8_mfma,
+                          filt=None):
+    """cosine_topk_gemm over an e4m3 index (see there); filt: the validated row-filter keywords, or None."""
     if products is not None:
         raise ValueError("an e4m3 index has one selection precision: products must be None")
     if shadow is not None:
         raise ValueError("shadow goes with an f32 index, not an e4m3 one")
     if row_scale is None:
         raise ValueError("an fp8 index needs row_scale (the per-row scale returned by quantize_rows_fp8)")
-    dev = _require_gpu(queries, index, row_scale)
+    dev = _require_gpu(queries, index, row_scale, *(filt or {}).values())
     scale_given = row_scale  # the caller's tensor object: what the cached norm verdict is keyed on
     q, x, row_scale = _topk_operands(queries, index, row_scale)
     Q, D = q.shape
@@ -513,7 +547,8 @@ def _cosine_topk_gemm_fp8(queries, index, k, row_scale, row_id_base, fallback, o
     native = True if fp8_mfma is None else bool(fp8_mfma)
 
     def scan():
-        return cosine_topk(q, x, k, row_scale=row_scale, row_id_base=row_id_base, out=out, method="scan", fp8_mfma=native)
+        return cosine_topk(q, x, k, row_scale=row_scale, row_id_base=row_id_base, out=out, method="scan", fp8_mfma=native,
+                           **(filt or {}))
 
     if Q == 0 or N == 0:
         return scan()
@@ -527,9 +562,15 @@ def _cosine_topk_gemm_fp8(queries, index, k, row_scale, row_id_base, fallback, o
     ws = _workspace(dev, "cosine_topk_gemm", int(lib.evi_cosine_topk_gemm_workspace_bytes(Q, N, D, int(k))))
     out_score, out_index = _topk_out(out, Q, k, dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.evi_cosine_topk_gemm_fp8(_ptr(q), Q, _ptr(x), N, D, _ptr(row_scale), int(k), int(row_id_base), int(native),
-                                            _ptr(out_score), _ptr(out_index), status.data_ptr(), ws.data_ptr(), ws.numel(),
-                                            _stream(dev)))
+    if filt is not None:
+        labels, allow = _topk_filter_operands(filt["row_mask"], filt["row_labels"], filt["query_allow"], Q, dev)
+        _lib.check(lib.evi_cosine_topk_gemm_filtered(_ptr(q), Q, _ptr(x), 3 if native else 2, N, D, _ptr(row_scale), _ptr(labels),
+                                                     _ptr(allow), int(k), int(row_id_base), 3, None, _ptr(out_score),
+                                                     _ptr(out_index), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    else:
+        _lib.check(lib.evi_cosine_topk_gemm_fp8(_ptr(q), Q, _ptr(x), N, D, _ptr(row_scale), int(k), int(row_id_base), int(native),
+                                                _ptr(out_score), _ptr(out_index), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                _stream(dev)))
     st = int(status.item())
     cosine_topk_gemm.last_status = st  # 0 proven; 1 gap test failed; 2 a candidate list overflowed (introspection / bench)
     if st != 0:

@@ -200,6 +200,24 @@ int evi_cosine_topk_gemm_fp8(const float* q, int Q, const void* idx_fp8, int64_t
 int evi_cosine_topk_gemm_fp8_selection(const float* q, int Q, const void* idx_fp8, int64_t N, int D,
                                        const float* row_scale, int native_mfma, float* out_scores, void* workspace,
                                        size_t workspace_bytes, void* stream);
+/* The many-query pass restricted by row labels and per-query allow-sets (the operands and the visibility rule of
+ * evi_cosine_topk_filtered), one entry point for the four index kinds:
+ *   kind   0 evi_cosine_topk_gemm, 1 evi_cosine_topk_gemm_f16, 2 evi_cosine_topk_gemm_fp8 with native_mfma = 0, 3 the same
+ *          with native_mfma != 0 (idx, row_scale and the limits on D and k as there).  Kinds 2 and 3 have one selection
+ *          precision: products must be 3 and shadow_bf16 null.
+ * With *status == 0 the outputs equal those of evi_cosine_topk_filtered of that kind bit for bit (the exact top-k of the
+ * rows visible to each query, (-inf, -1) past their number; an empty allow-set gives all (-inf, -1)); *status is set as by
+ * evi_cosine_topk_gemm, and a non-zero value means: discard the outputs and run evi_cosine_topk_filtered.  A hidden
+ * (query, row) pair never enters a candidate list, so the proof speaks of the visible rows alone; a query with fewer than
+ * k + reserve visible rows holds all of them and needs no proof.  The label byte is read only for a score that already
+ * passes the query's threshold.  Labels that hide long runs of rows in front of visible ones overflow a list (status 2).
+ * Workspace: evi_cosine_topk_gemm_workspace_bytes, unchanged.  A null row_labels or query_allow, or a kind outside 0..3,
+ * is EVI_ERR_INVALID, checked on the host before any device work. */
+int evi_cosine_topk_gemm_filtered(const float* q, int Q, const void* idx, int kind, int64_t N, int D,
+                                  const float* row_scale, const uint8_t* row_labels, const uint32_t* query_allow,
+                                  int k, int64_t row_id_base, int products, const void* shadow_bf16,
+                                  float* out_score, int64_t* out_index, int32_t* status,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* Two-stage exact scan: the result of evi_cosine_topk (ids and scores bit-identical) at half the HBM bytes per
  * batch, for an f32 index of rows with norm <= 1 (evi_row_normalize output; no row_scale) that is kept together

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised cross-check of the cosine top-k paths against the oracle's full score matrix: the f32 scan, the two-stage
-exact scan (must equal the scan bit for bit), the many-query GEMM-shaped pass (must equal the scan bit for bit), the f16 index
+exact scan (must equal the scan bit for bit), the many-query GEMM-shaped pass (must equal the scan bit for bit; with row labels
+and allow-sets: must equal the filtered scan bit for bit), the f16 index
 (overlap with the f32 result), shard merge (3 uneven shards == one pass) — over odd shapes: one row, k beyond the row count,
 duplicate and zero rows, Q not a multiple of 32, D not a multiple of 64 (D % 16 == 0 is the scan's documented limit).   python tools/fuzz_topk.py [cases] [seed]"""
 import os
@@ -48,6 +49,19 @@ def one_case(rng, dev):
             notes.append("gemm")
         except NotImplementedError:
             notes.append("gemm:unsupported")
+        # the filtered GEMM-shaped pass against the filtered scan: random labels 0..5 and tombstones, mixed allow-sets
+        labels = torch.from_numpy(rng.integers(0, 6, size=N).astype(np.uint8)).to(dev)
+        labels[torch.from_numpy(rng.integers(0, N, size=max(1, N // 50))).to(dev)] = int(rng.choice([32, 77, 255]))
+        sets = [0, 0xFFFFFFFF, 0b000101, 0b101010, int(rng.integers(0, 64))]
+        allow = torch.tensor([sets[j % len(sets)] for j in range(Q)], dtype=torch.int64, device=dev)
+        try:
+            sf, jf = ops.cosine_topk(qn, xn, k, method="scan", row_labels=labels, query_allow=allow)
+            sg, jg = ops.cosine_topk_gemm(qn, xn, k, check_norms=False, row_labels=labels, query_allow=allow)
+            assert torch.equal(jg, jf) and torch.equal(sg.view(torch.int32), sf.view(torch.int32)), \
+                "filtered GEMM-shaped pass differs from the filtered scan"
+            notes.append(f"gemm-filter(products {ops.cosine_topk_gemm.last_products}, status {ops.cosine_topk_gemm.last_status})")
+        except NotImplementedError:
+            notes.append("gemm-filter:unsupported")
     if N >= 97:  # three uneven shards merged == one pass
         cuts = [0, N // 5, N // 5 + (N // 2), N]
         parts = [ops.cosine_topk(qn, xn[cuts[j]: cuts[j + 1]].contiguous(), k, row_id_base=cuts[j]) for j in range(3)]
