@@ -1699,3 +1699,241 @@ extern "C" int evi_cosine_topk_two_stage_filtered(const float* q, int Q, const f
     return cosine_topk_two_stage_impl(q, Q, idx, shadow_f16, N, D, row_labels, query_allow, k, row_id_base, out_score, out_index,
                                       status, device_fallback, workspace, workspace_bytes, stream);
 }
+
+// =====================================================================================================
+// Per-query candidate lists: the exact top-k of the rows a query NAMES (a packed batch's node_embedding_ids cut by ptr,
+// edge_attr cut by edge_ptr) instead of the rows of the whole index — the reference's per-group arg-max
+// (scripts/build_retrieval_pipeline.py:856-874), generalised as evi_cosine_topk generalised it.
+//
+//   k_cand_ptr / k_cand_mark   cand_ptr checked, ids -> local rows + drop mask (the id rules of the header)
+//   evi_first_occurrence + evi_first_seen_rank (compact.hip)   per query: the distinct rows and their count
+//   k_cand_tiles               exclusive prefix of ceil(count / 16): which wave of the scoring grid serves which query
+//   k_cand_score               the ragged k_rescore: one wave per 16 distinct rows, the same chains -> the scan's bits
+//   k_cand_select              block_topk over a query's compacted (score, local row) pairs, write_topk
+//
+// Every grid comes from Q, T and k; nothing is read back.  Bound: the gather of the distinct rows (whole rows at random
+// places of HBM), then launch latency — seven short launches per call.
+// =====================================================================================================
+namespace evi {
+
+constexpr int kCandThreads = 1024;
+
+// seg_ptr = cand_ptr when 0 <= cand_ptr[i] <= cand_ptr[i + 1] <= T for every i; else every list is EMPTY and bit 2 goes
+// into *status.  (Clamping list by list would keep every read inside cand_ids, but lists that overlap would share their
+// de-duplication tables: a malformed call answers nothing instead of something that depends on the interleaving.)
+__global__ __launch_bounds__(kCandThreads) void k_cand_ptr(const int64_t* __restrict__ cand_ptr, int Q, int64_t T,
+                                                           int64_t* __restrict__ seg_ptr, int32_t* __restrict__ status) {
+    int bad = 0;
+    for (int i = threadIdx.x; i < Q; i += kCandThreads) {
+        const int64_t a = cand_ptr[i], b = cand_ptr[i + 1];
+        bad |= (a < 0 || b < a || b > T) ? 1 : 0;
+    }
+    const int any = __syncthreads_or(bad);
+    for (int i = threadIdx.x; i <= Q; i += kCandThreads) seg_ptr[i] = any ? 0 : cand_ptr[i];
+    if (any && threadIdx.x == 0 && status) atomicOr(status, 2);
+}
+
+// The id rules, before any address is formed from an id: g < 0 padding; g >= id_limit dropped + status bit 1;
+// g - row_id_base outside [0, N) not on this shard; else local row g - row_id_base.
+__global__ __launch_bounds__(256) void k_cand_mark(const int64_t* __restrict__ cand_ids, int64_t T, int64_t N, int64_t row_id_base,
+                                                   int64_t id_limit, int64_t* __restrict__ keys, uint8_t* __restrict__ drop,
+                                                   int32_t* __restrict__ status) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T) return;
+    const int64_t g = cand_ids[i];
+    const bool over = g >= 0 && g >= id_limit;
+    // g >= row_id_base: the difference is in [0, 2^64), exact in unsigned arithmetic whatever the signs
+    const uint64_t local = (uint64_t)g - (uint64_t)row_id_base;
+    const bool keep = g >= 0 && !over && g >= row_id_base && local < (uint64_t)N;
+    keys[i] = keep ? (int64_t)local : 0;
+    drop[i] = keep ? 0 : 1;
+    if (over && status) atomicOr(status, 1);
+}
+
+// tile_pre[i] = sum_{j < i} ceil(count[j] / 16), i = 0 .. Q: one workgroup, chunks of 1024 queries.
+__global__ __launch_bounds__(kCandThreads) void k_cand_tiles(const int32_t* __restrict__ count, int Q, int32_t* __restrict__ tile_pre) {
+    __shared__ int wave_tot[kCandThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int base = 0;
+    for (int c0 = 0; c0 < Q; c0 += kCandThreads) {
+        const int i = c0 + tid;
+        const int v = i < Q ? (count[i] + 15) / 16 : 0;
+        int incl = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int up = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += up;
+        }
+        __syncthreads();  // wave_tot may still be read from the previous chunk
+        if (lane == 63) wave_tot[wave] = incl;
+        __syncthreads();
+        int before = 0, tot = 0;
+#pragma unroll
+        for (int w = 0; w < kCandThreads / 64; ++w) {
+            const int c = wave_tot[w];
+            if (w < wave) before += c;
+            tot += c;
+        }
+        if (i < Q) tile_pre[i] = base + before + incl - v;
+        base += tot;
+    }
+    if (tid == 0) tile_pre[Q] = base;
+}
+
+// scores[p0 + c] = chain(q[qi], idx[row]) * row_scale[row], rows[p0 + c] = row for the c-th distinct row of query qi
+// (p0 = seg_ptr[qi], c < count[qi]).  Wave w serves tile w - tile_pre[qi] of the query whose tile range holds w; the grid
+// is sized from the host bound ceil(T / 16) + Q >= tile_pre[Q] and the waves beyond leave whole.  The query sits in row 0
+// of A and the 16 rows in the columns of B exactly as in k_rescore; lanes past the count read row 0 and write nothing.
+template <class RowT>
+__global__ __launch_bounds__(256) void k_cand_score(const float* __restrict__ q, int D, const RowT* __restrict__ idx,
+                                                    const float* __restrict__ row_scale, const int64_t* __restrict__ keys,
+                                                    const int64_t* __restrict__ seg_ptr, const int32_t* __restrict__ uniq_pos,
+                                                    const int32_t* __restrict__ count, const int32_t* __restrict__ tile_pre, int Q,
+                                                    float* __restrict__ scores, int32_t* __restrict__ rows) {
+    const int lane = threadIdx.x & 63;
+    const int n = lane & 15, g = lane >> 4;
+    const int64_t w = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (w >= (int64_t)tile_pre[Q]) return;  // whole waves only: the MFMAs below run with all 64 lanes
+    int lo = 0, hi = Q;  // tile_pre[lo] <= w < tile_pre[hi]
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if ((int64_t)tile_pre[mid] <= w) lo = mid; else hi = mid;
+    }
+    const int qi = lo;
+    const int64_t p0 = seg_ptr[qi];
+    const int m = count[qi];
+    const int c = (int)(w - tile_pre[qi]) * 16 + n;
+    const int64_t row = c < m ? keys[p0 + uniq_pos[p0 + c]] : -1;
+    const float dot = rescore_chain(q + (int64_t)qi * D, idx + (row >= 0 ? row : 0) * D, D, n, g);
+    if (g == 0 && c < m) {
+        scores[p0 + c] = row_scale ? dot * row_scale[row] : dot;
+        rows[p0 + c] = (int32_t)row;
+    }
+}
+
+// count == null: every list is empty (T == 0 or N == 0), the outputs are all padding.
+__global__ __launch_bounds__(kSelectThreads) void k_cand_select(const float* __restrict__ scores, const int32_t* __restrict__ rows,
+                                                                const int64_t* __restrict__ seg_ptr, const int32_t* __restrict__ count,
+                                                                int k, int64_t row_id_base, float* __restrict__ out_score,
+                                                                int64_t* __restrict__ out_index) {
+    __shared__ SelectShared sh;
+    const int qi = blockIdx.x;
+    const int m0 = count ? count[qi] : 0;
+    const int64_t p0 = count ? seg_ptr[qi] : 0;
+    const float* s = scores + p0;
+    const int32_t* r = rows + p0;
+    auto load = [&](int64_t i) -> uint64_t { return make_key(s[i], (uint32_t)r[i]); };
+    const int m = block_topk(sh, load, m0, k);
+    write_topk(sh, m, qi, k, row_id_base, out_score, out_index);
+}
+
+struct CandLayout {
+    size_t seg_ptr, keys, drop, first, rank, uniq_pos, count, tile_pre, scores, rows, table, table_bytes, total;
+};
+
+static CandLayout cand_layout(int Q, int64_t T) {
+    CandLayout L;
+    Bump m;
+    L.seg_ptr = m.take((size_t)(Q + 1) * sizeof(int64_t));
+    L.keys = m.take((size_t)T * sizeof(int64_t));
+    L.drop = m.take((size_t)T);
+    L.first = m.take((size_t)T * sizeof(int32_t));
+    L.rank = m.take((size_t)T * sizeof(int32_t));
+    L.uniq_pos = m.take((size_t)T * sizeof(int32_t));
+    L.count = m.take((size_t)Q * sizeof(int32_t));
+    L.tile_pre = m.take((size_t)(Q + 1) * sizeof(int32_t));
+    L.scores = m.take((size_t)T * sizeof(float));
+    L.rows = m.take((size_t)T * sizeof(int32_t));
+    L.table_bytes = evi_first_occurrence_workspace_bytes(T, Q);
+    L.table = m.take(L.table_bytes);
+    L.total = m.total;
+    return L;
+}
+
+template <class RowT>
+static void launch_cand_score(hipStream_t st, int64_t waves, const float* q, int D, const void* idx, const float* row_scale,
+                              const int64_t* keys, const int64_t* seg_ptr, const int32_t* uniq_pos, const int32_t* count,
+                              const int32_t* tile_pre, int Q, float* scores, int32_t* rows) {
+    launch_timed(kTimeCosineScore, k_cand_score<RowT>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, q, D,
+                 static_cast<const RowT*>(idx), row_scale, keys, seg_ptr, uniq_pos, count, tile_pre, Q, scores, rows);
+}
+
+}  // namespace evi
+
+extern "C" size_t evi_cosine_topk_candidates_workspace_bytes(int Q, int64_t T, int k) {
+    if (Q < 0 || T < 0 || k <= 0) return 0;
+    return cand_layout(Q, T).total;
+}
+
+extern "C" int evi_cosine_topk_candidates(const float* q, int Q, const void* idx, int kind, int64_t N, int D, const float* row_scale,
+                                          const int64_t* cand_ids, const int64_t* cand_ptr, int64_t T, int k, int64_t row_id_base,
+                                          int64_t id_limit, float* out_score, int64_t* out_index, int32_t* status, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    EVI_REQUIRE(kind >= kIdxF32 && kind <= kIdxFp8Mfma, "evi_cosine_topk_candidates: kind must be 0 (f32), 1 (f16), 2 (e4m3 widened) "
+                "or 3 (e4m3 native MFMA), got %d", kind);
+    EVI_REQUIRE(Q >= 0 && N >= 0 && T >= 0, "evi_cosine_topk_candidates: need Q >= 0, N >= 0 and T >= 0, got Q=%d N=%lld T=%lld", Q,
+                (long long)N, (long long)T);
+    EVI_REQUIRE(N < (int64_t)0x7FFFFFFF, "evi_cosine_topk_candidates: a shard holds at most 2^31-1 rows, got %lld", (long long)N);
+    EVI_REQUIRE(T / 16 + Q < (int64_t)0x7FFFFFFF - 1, "evi_cosine_topk_candidates: T / 16 + Q must stay below 2^31, got T=%lld Q=%d",
+                (long long)T, Q);
+    EVI_REQUIRE(T <= (int64_t)0x7FFFFFFF, "evi_cosine_topk_candidates: at most 2^31-1 list entries per call, got %lld", (long long)T);
+    EVI_REQUIRE(k >= 1 && k <= EVI_TOPK_MAX_K, "evi_cosine_topk_candidates: k must be in [1, %d], got %d", EVI_TOPK_MAX_K, k);
+    if (D < 16 || D % 16 != 0 || D > 1280)
+        return fail(EVI_ERR_UNSUPPORTED, "evi_cosine_topk_candidates: D must be a multiple of 16 in [16, 1280], got %d", D);
+    if (kind == kIdxF16 && D % 32 != 0)
+        return fail(EVI_ERR_UNSUPPORTED, "evi_cosine_topk_candidates: an f16 index needs D to be a multiple of 32, got %d", D);
+    if (kind >= kIdxFp8Widen && D % 64 != 0)
+        return fail(EVI_ERR_UNSUPPORTED, "evi_cosine_topk_candidates: an e4m3 index needs D to be a multiple of 64, got %d", D);
+    EVI_REQUIRE(kind < kIdxFp8Widen || row_scale,
+                "evi_cosine_topk_candidates: row_scale (the per-row dequantisation scale) is required for an e4m3 index");
+    if (Q == 0) return EVI_OK;
+    EVI_REQUIRE(q && cand_ptr && out_score && out_index && workspace && (T == 0 || cand_ids) && (N == 0 || idx),
+                "evi_cosine_topk_candidates: null pointer");
+    const CandLayout L = cand_layout(Q, T);
+    if (workspace_bytes < L.total)
+        return fail(EVI_ERR_NOMEM, "evi_cosine_topk_candidates: workspace %zu B < %zu B", workspace_bytes, L.total);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* base = static_cast<char*>(workspace);
+    int64_t* seg_ptr = reinterpret_cast<int64_t*>(base + L.seg_ptr);
+    int64_t* keys = reinterpret_cast<int64_t*>(base + L.keys);
+    uint8_t* drop = reinterpret_cast<uint8_t*>(base + L.drop);
+    int32_t* first = reinterpret_cast<int32_t*>(base + L.first);
+    int32_t* rank = reinterpret_cast<int32_t*>(base + L.rank);
+    int32_t* uniq_pos = reinterpret_cast<int32_t*>(base + L.uniq_pos);
+    int32_t* count = reinterpret_cast<int32_t*>(base + L.count);
+    int32_t* tile_pre = reinterpret_cast<int32_t*>(base + L.tile_pre);
+    float* scores = reinterpret_cast<float*>(base + L.scores);
+    int32_t* rows = reinterpret_cast<int32_t*>(base + L.rows);
+
+    hipLaunchKernelGGL(k_cand_ptr, dim3(1), dim3(kCandThreads), 0, st, cand_ptr, Q, T, seg_ptr, status);
+    EVI_LAUNCH_CHECK();
+    if (T > 0) {
+        hipLaunchKernelGGL(k_cand_mark, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, cand_ids, T, N, row_id_base, id_limit, keys,
+                           drop, status);
+        EVI_LAUNCH_CHECK();
+    }
+    if (T == 0 || N == 0) {  // nothing to score: all padding
+        hipLaunchKernelGGL(k_cand_select, dim3(Q), dim3(kSelectThreads), 0, st, scores, rows, seg_ptr, (const int32_t*)nullptr, k,
+                           row_id_base, out_score, out_index);
+        EVI_LAUNCH_CHECK();
+        return EVI_OK;
+    }
+    int rc = evi_first_occurrence(keys, 1, T, seg_ptr, Q, drop, first, base + L.table, L.table_bytes, stream);
+    if (rc != EVI_OK) return rc;
+    rc = evi_first_seen_rank(first, T, seg_ptr, Q, nullptr, rank, count, uniq_pos, stream);
+    if (rc != EVI_OK) return rc;
+    hipLaunchKernelGGL(k_cand_tiles, dim3(1), dim3(kCandThreads), 0, st, count, Q, tile_pre);
+    EVI_LAUNCH_CHECK();
+    const int64_t waves = (T + 15) / 16 + Q;  // >= sum over queries of ceil(count / 16)
+    switch ((IndexKind)kind) {
+        case kIdxF32: launch_cand_score<float>(st, waves, q, D, idx, row_scale, keys, seg_ptr, uniq_pos, count, tile_pre, Q, scores, rows); break;
+        case kIdxF16: launch_cand_score<_Float16>(st, waves, q, D, idx, row_scale, keys, seg_ptr, uniq_pos, count, tile_pre, Q, scores, rows); break;
+        case kIdxFp8Widen: launch_cand_score<Fp8WidenRow>(st, waves, q, D, idx, row_scale, keys, seg_ptr, uniq_pos, count, tile_pre, Q, scores, rows); break;
+        default: launch_cand_score<Fp8MfmaRow>(st, waves, q, D, idx, row_scale, keys, seg_ptr, uniq_pos, count, tile_pre, Q, scores, rows); break;
+    }
+    EVI_LAUNCH_CHECK();
+    launch_timed(kTimeSelect, k_cand_select, dim3(Q), dim3(kSelectThreads), 0, st, scores, rows, seg_ptr, count, k, row_id_base,
+                 out_score, out_index);
+    EVI_LAUNCH_CHECK();
+    return EVI_OK;
+}

@@ -305,6 +305,41 @@ class ShardedIndex:
         dist.all_gather_into_tensor(self._gather_i.view(self.world * Q, k), i.contiguous(), group=self.group)
         return self._merge(self._gather_s, self._gather_i)
 
+    def topk_candidates(self, queries: torch.Tensor, candidates: torch.Tensor, k: int,
+                        cand_ptr: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Global top-k of each query's own candidate rows (ops.cosine_topk_candidates) — identical on every rank.  Every
+        rank gets the full lists of GLOBAL row ids, as it gets the full queries, and scores the rows of its own shard
+        (row_id_base = its first row, id_limit = the index's row count); the records then take the exchange and the merge
+        of `topk`.  Synchronous path only."""
+        from . import _lib, ops
+
+        if self._local_topk is not _default_local_topk:
+            raise ValueError("a custom local_topk takes no candidate lists")
+        total = self.bounds[-1]
+
+        def local(out):
+            return ops.cosine_topk_candidates(queries, self.shard, candidates, k, cand_ptr=cand_ptr, row_scale=self.row_scale,
+                                              row_id_base=self.row_begin, id_limit=total,
+                                              fp8_mfma=self.fp8_mfma if self.shard.dtype == torch.uint8 else None, out=out)
+
+        Q = queries.size(0)
+        if self._exchange and self._packed_ok and queries.is_cuda and Q > 0:
+            rec = int(_lib.load().evi_topk_packed_bytes(Q, k))
+            if self._packed_local is None or self._packed_local.numel() != rec:
+                self._packed_local = torch.empty(rec, dtype=torch.uint8, device=queries.device)
+                self._packed_all = torch.empty(self.world * rec, dtype=torch.uint8, device=queries.device)
+            local(ops.topk_packed_views(self._packed_local, Q, k))
+            self._exchange_fn(self._packed_all, self._packed_local)
+            return ops.topk_merge_packed(self._packed_all, self.world, Q, k)
+        s, i = local(None)
+        if self.world == 1:
+            return s, i
+        gs = torch.empty((self.world, Q, k), dtype=torch.float32, device=s.device)
+        gi = torch.empty((self.world, Q, k), dtype=torch.int64, device=s.device)
+        dist.all_gather_into_tensor(gs.view(self.world * Q, k), s.contiguous(), group=self.group)
+        dist.all_gather_into_tensor(gi.view(self.world * Q, k), i.contiguous(), group=self.group)
+        return self._merge(gs, gi)
+
 
 def _topk_packed(self: "ShardedIndex", queries: torch.Tensor, k: int, row_filter: Optional[dict] = None):
     from . import _lib, ops

@@ -343,6 +343,82 @@ def _cosine_topk_filtered(queries, index, k, row_scale, row_id_base, workspace, 
     return out_score, out_index
 
 
+def cosine_topk_candidates(
+    queries: torch.Tensor,
+    index: torch.Tensor,
+    candidates: torch.Tensor,
+    k: int,
+    *,
+    cand_ptr: Optional[torch.Tensor] = None,
+    row_scale: Optional[torch.Tensor] = None,
+    row_id_base: int = 0,
+    id_limit: Optional[int] = None,
+    fp8_mfma: Optional[bool] = None,
+    status: Optional[torch.Tensor] = None,
+    workspace: Optional[torch.Tensor] = None,
+    out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k of each query's OWN candidate rows: query i is ranked against the distinct valid rows its list names, not
+    against the index (a packed batch: `node_embedding_ids` cut by `ptr`, `edge_attr` cut by `edge_ptr`).  Returns
+    (scores [Q,k] f32, ids [Q,k] i64), ordered (score desc, id asc), (-inf, -1) past the number of distinct valid rows: the
+    ids and the score bits of cosine_topk(queries[i:i+1], index[sorted(unique(list_i))], k, method="scan"), mapped back.
+    candidates: int64 [Q, C] padded with -1 (cand_ptr must be None), or int64 / int32 [T] with cand_ptr int64 [Q + 1].
+    Ids are GLOBAL rows: `index` holds rows [row_id_base, row_id_base + N).  An id < 0 is padding; an id >= id_limit
+    (default row_id_base + N) is skipped and sets bit 1 of `status`; an id of another shard is skipped silently; a
+    cand_ptr that is not non-decreasing inside [0, T] sets bit 2 and empties every list.  `status` (int32 [1], zeroed by
+    the caller) is only written, never read back here; the call does not synchronise and can be captured in a graph.
+    index kinds, row_scale and fp8_mfma as in cosine_topk.  No row filter and no method: this is one path."""
+    if queries.dim() != 2 or index.dim() != 2:
+        raise ValueError("queries and index must be 2D")
+    if not isinstance(candidates, torch.Tensor) or candidates.dim() not in (1, 2):
+        raise ValueError("candidates must be a tensor: int64 [Q, C] padded with -1, or int64 / int32 [T] with cand_ptr")
+    if candidates.dim() == 2:
+        if candidates.dtype != torch.int64:
+            raise ValueError(f"candidates [Q, C] must be int64, got {candidates.dtype}")
+        if cand_ptr is not None:
+            raise ValueError("cand_ptr goes with a 1-D candidate list: a [Q, C] list is cut into rows of C entries")
+        if candidates.size(0) != queries.size(0):
+            raise ValueError(f"candidates [Q, C] must have one row per query ({queries.size(0)}), got {candidates.size(0)}")
+    else:
+        if candidates.dtype not in (torch.int64, torch.int32):
+            raise ValueError(f"candidates [T] must be int64 or int32, got {candidates.dtype}")
+        if cand_ptr is None:
+            raise ValueError("a 1-D candidate list needs cand_ptr (int64 [Q + 1])")
+        if cand_ptr.dtype != torch.int64 or cand_ptr.dim() != 1:
+            raise ValueError(f"cand_ptr must be a 1-D int64 tensor, got {cand_ptr.dtype} {tuple(cand_ptr.shape)}")
+        if cand_ptr.numel() != queries.size(0) + 1:
+            raise ValueError(f"cand_ptr must have Q + 1 = {queries.size(0) + 1} entries, got {cand_ptr.numel()}")
+    if fp8_mfma and index.dtype != torch.uint8:
+        raise ValueError("fp8_mfma goes with an e4m3 (uint8) index")
+    if index.dtype == torch.uint8 and row_scale is None:
+        raise ValueError("an fp8 index needs row_scale (the per-row scale returned by quantize_rows_fp8)")
+    if status is not None and (status.dtype != torch.int32 or status.numel() != 1):
+        raise ValueError("status must be an int32 tensor with one element")
+    dev = _require_gpu(queries, index, candidates, cand_ptr, row_scale, status, workspace)
+    q, x, row_scale = _topk_operands(queries, index, row_scale)
+    Q, D = q.shape
+    N = x.shape[0]
+    k = int(k)
+    out_score, out_index = _topk_out(out, Q, k, dev)
+    if candidates.dim() == 2:
+        cand_ptr = torch.arange(Q + 1, dtype=torch.int64, device=dev) * candidates.size(1)
+    ids = candidates.contiguous().view(-1) if candidates.dtype == torch.int64 else candidates.to(torch.int64).contiguous()
+    cand_ptr = cand_ptr.contiguous()
+    T = ids.numel()
+    if fp8_mfma is None:
+        fp8_mfma = x.dtype == torch.uint8
+    kind = {torch.float16: 1, torch.uint8: 3 if fp8_mfma else 2}.get(x.dtype, 0)
+    lib = _lib.load()
+    if workspace is None:
+        workspace = _workspace(dev, "cosine_topk_candidates", int(lib.evi_cosine_topk_candidates_workspace_bytes(Q, T, k)))
+    limit = int(row_id_base) + N if id_limit is None else int(id_limit)
+    # argument checks (D, k) run in the library even for Q == 0; its pointers may then be null
+    _lib.check(lib.evi_cosine_topk_candidates(_ptr(q), Q, _ptr(x), kind, N, D, _ptr(row_scale), _ptr(ids), cand_ptr.data_ptr(), T, k,
+                                              int(row_id_base), limit, _ptr(out_score), _ptr(out_index), _ptr(status),
+                                              workspace.data_ptr(), _nbytes(workspace), _stream(dev)))
+    return out_score, out_index
+
+
 cosine_topk.last_method = None  # which path the last call took: "scan" | "gemm" | "two_stage" (introspection / tests)
 
 

@@ -157,6 +157,33 @@ int evi_cosine_topk_filtered(const float* q, int Q, const void* idx, int kind, i
                              const uint8_t* row_labels, const uint32_t* query_allow, int k, int64_t row_id_base,
                              float* out_score, int64_t* out_index, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Exact top-k over PER-QUERY CANDIDATE LISTS: query i is ranked against the rows its own list names, not against the
+ * index — a packed batch's node_embedding_ids cut by ptr, or edge_attr cut by edge_ptr, into the HBM-resident tables
+ * (the per-group arg-max of scripts/build_retrieval_pipeline.py:856-874, generalised as evi_cosine_topk generalised it).
+ *   kind, idx, row_scale   as evi_cosine_topk_filtered (row_scale required for kinds 2 and 3); D as the scan of that kind
+ *   cand_ids   [T] i64      GLOBAL row ids, any order, repeats allowed
+ *   cand_ptr   [Q + 1] i64  query i owns cand_ids[cand_ptr[i] .. cand_ptr[i + 1])
+ *   row_id_base, id_limit   idx holds the global rows [row_id_base, row_id_base + N); ids live in [0, id_limit)
+ *   status     device i32 or NULL; bits are ORed in, the CALLER zeroes it (as for evi_gather_rows)
+ * Id rules, applied on the device before any address is formed from an id: g < 0 is padding (ignored); g >= id_limit is
+ * ignored and ORs 1 into *status; g - row_id_base outside [0, N) is a row of another shard (ignored); otherwise the row
+ * is idx[g - row_id_base] and the id written is g.  A cand_ptr that is not 0 <= cand_ptr[i] <= cand_ptr[i + 1] <= T
+ * throughout ORs 2 into *status and makes EVERY list empty (all outputs padding); cand_ids is never read outside [0, T).
+ * Result per query: the exact top-k of the DISTINCT valid rows of its list, ordered (score desc, id asc), slots past their
+ * number filled with (-inf, -1).  Ids and score bits equal those of the scan of that kind over the index compacted to
+ * those rows (ascending), mapped back; a row that is not listed never appears, whatever its score (NaN included).  Each
+ * distinct row is read once per query.  Nothing is read back and nothing synchronises; every grid size comes from Q, T
+ * and k, so the call can be captured on one stream and replayed over new contents of the same shapes.
+ * Q == 0, T == 0 and N == 0 are valid (all padding, no scoring launch).  Host refusals before any device work: D outside
+ * the kind's rule EVI_ERR_UNSUPPORTED; k outside 1..EVI_TOPK_MAX_K, a missing row_scale for e4m3, a null pointer, N >=
+ * 2^31 - 1 or T >= 2^31 EVI_ERR_INVALID; a workspace below evi_cosine_topk_candidates_workspace_bytes(Q, T, k) (about
+ * 40 B per list entry) EVI_ERR_NOMEM. */
+size_t evi_cosine_topk_candidates_workspace_bytes(int Q, int64_t T, int k);
+int evi_cosine_topk_candidates(const float* q, int Q, const void* idx, int kind, int64_t N, int D, const float* row_scale,
+                               const int64_t* cand_ids, const int64_t* cand_ptr, int64_t T, int k, int64_t row_id_base,
+                               int64_t id_limit, float* out_score, int64_t* out_index, int32_t* status, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 /* The same result as evi_cosine_topk (ids and scores bit-identical) for MANY queries (Q in the hundreds; f32
  * index, rows of unit norm after row_scale, D % 16 == 0, k <= 1365): the scores of all queries against a
  * slab of rows are formed as one split-bf16 MFMA GEMM and used only to SELECT k + reserve candidates per
