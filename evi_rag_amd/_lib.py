@@ -129,6 +129,10 @@ _SIGNATURES = {
     "evi_bfs_levels_edges": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_int64, _P, _P, _P, _P, c_int, _P, _P]),
     "evi_shortest_path_pairs": (c_int, [c_int, _P, _P, _P, _P, c_int, _P, _P, _P, c_int64, _P, _P, c_int, _P, _P, _P,
                                         _P, _P, _P]),
+    "evi_canonical_edges_lds_capacity": (c_int, []),
+    "evi_canonical_edges_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "evi_canonical_edges": (c_int, [c_int, _P, c_int64, _P, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, c_int64, c_int, _P, _P, _P, _P,
+                                    _P, _P, c_size_t, _P]),
     "evi_node_softmax_logit_workspace_bytes": (c_size_t, [c_int64]),
     "evi_node_softmax_logit": (c_int, [_P, _P, c_int64, c_int64, _P, _P, c_size_t, _P]),
     "evi_select_start_edges": (c_int, [_P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64, c_float, c_int, c_int, _P,

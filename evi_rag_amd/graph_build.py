@@ -208,11 +208,20 @@ def validate_graph_record(graph: GraphRecord) -> None:
 
 def build_graphs(samples: Sequence, entity_vocab, relation_vocab, graph_ids: Sequence[str], *,
                  path_mode: str = "undirected", dedup_edges: bool = True, validate_graph_edges: bool = True,
-                 remove_self_loops: bool = True) -> List[GraphRecord]:
+                 remove_self_loops: bool = True, canonicalize_relations: bool = False,
+                 question_emb_norm: Optional[torch.Tensor] = None,
+                 relation_emb_norm: Optional[torch.Tensor] = None) -> List[GraphRecord]:
     """A chunk of `Sample`s (attributes graph, q_entity, a_entity, answer_subgraph) -> GraphRecords.
     The vocabularies are consulted exactly as the reference does: entity_id / embedding_id once per new
-    node in first-seen order, relation_id once per kept edge in edge order."""
+    node in first-seen order, relation_id once per kept edge in edge order.
+
+    canonicalize_relations (the reference's embedding_cfg.canonicalize_relations, :1352-1355): the positive edges and pair
+    lists of the whole chunk are canonicalised in one device pass (`labelling.canonicalize_positive_edges_batch`) once the
+    relation ids are known and before the records are validated; question_emb_norm [len(samples), D] and relation_emb_norm
+    [R, D] (row = relation id) are the normalised embeddings."""
     path_mode = _validate_path_mode(path_mode)
+    if canonicalize_relations and (question_emb_norm is None or relation_emb_norm is None):
+        raise RuntimeError("Canonicalization requested but embeddings are missing.")
     tri, subs, qs, as_, ent_names = [], [], [], [], []
     rel_names: List[List[str]] = []
     for sample in samples:
@@ -247,9 +256,18 @@ def build_graphs(samples: Sequence, entity_vocab, relation_vocab, graph_ids: Seq
             edge_relation_ids=[relation_vocab.relation_id(rel_names[s][c]) for c in cg.edge_rel.tolist()],
             positive_triple_mask=list(positive), pair_start_node_locals=list(ps), pair_answer_node_locals=list(pa),
             pair_edge_local_ids=list(pe), pair_edge_counts=list(pc), pair_shortest_lengths=list(pl))
-        if validate_graph_edges:
+        if validate_graph_edges and not canonicalize_relations:
             validate_graph_record(rec)
         records.append(rec)
+    if canonicalize_relations and records:
+        canon = labelling.canonicalize_positive_edges_batch(
+            [r.edge_src for r in records], [r.edge_dst for r in records], [r.edge_relation_ids for r in records],
+            [r.positive_triple_mask for r in records], [r.pair_edge_local_ids for r in records],
+            [r.pair_edge_counts for r in records], question_emb_norm, relation_emb_norm)
+        for rec, (keep, ids, counts) in zip(records, canon):
+            rec.positive_triple_mask, rec.pair_edge_local_ids, rec.pair_edge_counts = keep, ids, counts
+            if validate_graph_edges:
+                validate_graph_record(rec)
     return records
 
 

@@ -128,7 +128,7 @@ def _upload_packed(dev: torch.device, arrays: Sequence[np.ndarray]) -> List[torc
     buf = torch.from_numpy(host).to(dev, non_blocking=True)
     out = []
     for a, o in zip(arrays, offs):
-        dt = {np.dtype(np.int64): torch.int64, np.dtype(np.int32): torch.int32}[a.dtype]
+        dt = {np.dtype(np.int64): torch.int64, np.dtype(np.int32): torch.int32, np.dtype(np.uint8): torch.uint8}[a.dtype]
         out.append(buf[o: o + a.nbytes].view(dt))
     return out
 
@@ -167,9 +167,10 @@ class FlatPairLabels:
     reference's per-graph 6-tuples on demand."""
 
     def __init__(self, B, E, edge_ptr_h, mask, pair_len, pair_count, pair_edge_off, pair_edge_ids, pair_graph_h,
-                 pair_start_h, pair_answer_h, pair_ptr_h):
+                 pair_start_h, pair_answer_h, pair_ptr_h, edge_ptr=None):
         self.B, self.E, self.P = int(B), int(E), int(pair_graph_h.shape[0])
         self.edge_ptr_h = edge_ptr_h
+        self.edge_ptr = edge_ptr  # [B + 1] i64 on the device when the producer had it (canonicalize_flat uploads it otherwise)
         self.mask, self.pair_len, self.pair_count = mask, pair_len, pair_count
         self.pair_edge_off, self.pair_edge_ids = pair_edge_off, pair_edge_ids
         self.pair_graph_h, self.pair_start_h, self.pair_answer_h, self.pair_ptr_h = pair_graph_h, pair_start_h, pair_answer_h, pair_ptr_h
@@ -251,7 +252,7 @@ def label_pairs_flat(edge_index: torch.Tensor, node_ptr: torch.Tensor, edge_ptr:
     if P == 0:
         z = np.empty(0, np.int64)
         return FlatPairLabels(B, E, edge_ptr_h, mask, empty(torch.int32), empty(torch.int32), torch.zeros(1, dtype=torch.int64, device=dev),
-                              empty(torch.int64), z, z, z, pair_ptr_h)
+                              empty(torch.int64), z, z, z, pair_ptr_h, edge_ptr=eptr)
     s_start = np.concatenate([[0], np.cumsum(s_cnt)])[:-1]
     a_start = np.concatenate([[0], np.cumsum(a_cnt)])[:-1]
     pg = np.repeat(np.arange(B, dtype=np.int64), ppg)
@@ -300,7 +301,7 @@ def label_pairs_flat(edge_index: torch.Tensor, node_ptr: torch.Tensor, edge_ptr:
     _lib.check(lib.evi_shortest_path_pairs(1, *args, plen.data_ptr(), pcnt.data_ptr(), mask.data_ptr(), poff.data_ptr(),
                                            pids.data_ptr(), st))
     return FlatPairLabels(B, E, edge_ptr_h, mask, plen, pcnt, poff, pids, pg, seeds_u[seed_job] - node_ptr_h[pg],
-                          pan - node_ptr_h[pg], pair_ptr_h)
+                          pan - node_ptr_h[pg], pair_ptr_h, edge_ptr=eptr)
 
 
 def shortest_path_union_mask_by_pair_batch(gb: GraphBatch, sources: Sequence[Sequence[int]],
@@ -480,6 +481,164 @@ def canonicalize_positive_edges(edge_src: Sequence[int], edge_dst: Sequence[int]
     return keep_mask, new_ids, new_counts
 
 
+class CanonicalPairLabels(FlatPairLabels):
+    """`FlatPairLabels` after `canonicalize_flat`: `mask` is the keep mask, `pair_count` / `pair_edge_off` / `pair_edge_ids`
+    are the filtered lists (same slots, ids in their original order), `pair_len` and the host fields are the input's.
+
+      status  [1] i32 on the device — deferred faults: bit 0 a relation id outside [0, R) on a scored edge (it was scored
+              clamped), bit 1 a relation score that is not finite.  `check_deferred()` reads it (one synchronisation)."""
+
+    def __init__(self, *args, status: torch.Tensor, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.status = status
+
+    def check_deferred(self) -> None:
+        st = int(self.status.item())
+        if st & 1:
+            raise ValueError("canonicalize_flat: a relation id outside [0, num_relations) on a positive edge that had to be scored")
+        if st & 2:
+            raise ValueError("canonicalize_flat: a relation score is not finite (NaN or inf in the normalised embeddings)")
+
+    def per_graph(self, valid_ids: Optional[Sequence[np.ndarray]] = None, orig_counts: Optional[Sequence[int]] = None):
+        self.check_deferred()
+        return super().per_graph(valid_ids, orig_counts)
+
+
+def _check_canonical_embeddings(question_emb_norm: torch.Tensor, relation_emb_norm: torch.Tensor, question_dim: int) -> None:
+    """The reference's checks (_canonicalize_graph_edges, :905-912), for questions held as `question_dim`-D rows."""
+    if question_emb_norm.numel() == 0:
+        raise ValueError("question_embedding is empty")
+    if relation_emb_norm.numel() == 0:
+        raise ValueError("relation_embeddings are empty; cannot canonicalize positives.")
+    if relation_emb_norm.dim() != 2 or question_emb_norm.dim() != question_dim:
+        raise ValueError("Embeddings must be 2D (relations) and 1D (question) for canonicalization.")
+    if int(relation_emb_norm.size(1)) != int(question_emb_norm.size(-1)):
+        raise ValueError("Question embedding dim does not match relation embedding dim.")
+
+
+def canonicalize_flat(flat: FlatPairLabels, edge_index: torch.Tensor, edge_relation_ids: torch.Tensor,
+                      question_emb_norm: torch.Tensor, relation_emb_norm: torch.Tensor) -> CanonicalPairLabels:
+    """`_canonicalize_graph_edges` (scripts/build_retrieval_pipeline.py:877-932) for every graph of a labelled batch at once,
+    on flat device arrays: among the parallel positive edges of one unordered node pair the edge whose relation is most
+    cosine-similar to the graph's question survives (first maximum in (relation_id, edge id) order), and the pair lists keep
+    the surviving ids in their order.
+
+      flat: what `label_pairs_flat` returned; edge_index [2, E] i64 and edge_relation_ids [E] i64 as in the collated batch;
+      question_emb_norm [B, D] f32 (one normalised question per graph), relation_emb_norm [R, D] f32.
+
+    Device work only: evi_canonical_edges pass 0 (keep mask, counts), a cumsum, pass 1 (ids).  Nothing is read back — faults
+    of the data are deferred into `status` — and the new id buffer has the capacity of the input's."""
+    dev = ops._require_gpu(flat.mask, edge_index, edge_relation_ids, question_emb_norm, relation_emb_norm)
+    B, E, P = flat.B, flat.E, flat.P
+    if E > 0:
+        _check_canonical_embeddings(question_emb_norm, relation_emb_norm, 2)
+        if int(question_emb_norm.size(0)) != B:
+            raise ValueError(f"question_emb_norm holds {int(question_emb_norm.size(0))} rows for {B} graphs")
+    ei = ops._i64c(edge_index, "edge_index")
+    rel = ops._i64c(edge_relation_ids.view(-1), "edge_relation_ids")
+    if ei.dim() != 2 or ei.size(0) != 2 or ei.size(1) != E or rel.numel() != E:
+        raise ValueError(f"edge_index must be [2, {E}] and edge_relation_ids [{E}], got {tuple(ei.shape)} and {tuple(rel.shape)}")
+    if flat.edge_ptr is None:
+        flat.edge_ptr = torch.from_numpy(np.ascontiguousarray(flat.edge_ptr_h, dtype=np.int64)).to(dev)
+    qn = ops._f32c(question_emb_norm, "question_emb_norm")
+    rn = ops._f32c(relation_emb_norm, "relation_emb_norm")
+    R, D = (int(rn.size(0)), int(rn.size(1))) if E > 0 else (0, 1)
+    keep = torch.empty(max(E, 1), dtype=torch.uint8, device=dev)
+    new_cnt = torch.empty(P, dtype=torch.int32, device=dev)
+    new_off = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+    new_ids = torch.empty(flat.pair_edge_ids.numel(), dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    ws = ops._workspace(dev, "canonical", int(lib.evi_canonical_edges_workspace_bytes(E, B, D)))
+    args = (ops._ptr(ei), E, ops._ptr(flat.edge_ptr), B, ops._ptr(rel), flat.mask.data_ptr(), ops._ptr(flat.pair_count),
+            flat.pair_edge_off.data_ptr(), ops._ptr(flat.pair_edge_ids), P, ops._ptr(qn), ops._ptr(rn), R, D, keep.data_ptr(),
+            ops._ptr(new_cnt), new_off.data_ptr(), ops._ptr(new_ids), status.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream(dev))
+    _lib.check(lib.evi_canonical_edges(0, *args))
+    if P > 0:
+        torch.cumsum(new_cnt, 0, dtype=torch.int64, out=new_off[1:])
+        _lib.check(lib.evi_canonical_edges(1, *args))
+    return CanonicalPairLabels(B, E, flat.edge_ptr_h, keep, flat.pair_len, new_cnt, new_off, new_ids, flat.pair_graph_h,
+                               flat.pair_start_h, flat.pair_answer_h, flat.pair_ptr_h, edge_ptr=flat.edge_ptr, status=status)
+
+
+def canonicalize_positive_edges_batch(edge_src: Sequence[Sequence[int]], edge_dst: Sequence[Sequence[int]],
+                                      edge_relation_ids: Sequence[Sequence[int]], positive_mask: Sequence[Sequence[bool]],
+                                      pair_edge_local_ids: Sequence[Sequence[int]], pair_edge_counts: Sequence[Sequence[int]],
+                                      question_embedding_norm: torch.Tensor, relation_embeddings_norm: torch.Tensor):
+    """`canonicalize_positive_edges` for a chunk of graphs: every argument but the relation table is a sequence over the graphs
+    (question_embedding_norm: [B, D], or B vectors of D).  One packed upload, `canonicalize_flat`, one read-back; returns
+    [(keep_mask, new_pair_edge_local_ids, new_pair_edge_counts)] with the reference's early returns per graph: an empty mask
+    or no positive edge gives the inputs back, empty pair lists come back as given beside the keep mask."""
+    B = len(edge_src)
+    masks = [np.asarray(m, dtype=bool).reshape(-1) for m in positive_mask]
+    srcs = [np.asarray(a, np.int64).reshape(-1) for a in edge_src]
+    untouched = [srcs[g].shape[0] == 0 or not masks[g].any() for g in range(B)]
+    if all(untouched):
+        return [(list(positive_mask[g]), list(pair_edge_local_ids[g]), list(pair_edge_counts[g])) for g in range(B)]
+    if not torch.is_tensor(question_embedding_norm):
+        question_embedding_norm = torch.stack([q.view(-1) for q in question_embedding_norm])
+    _check_canonical_embeddings(question_embedding_norm, relation_embeddings_norm, 2)
+    if int(question_embedding_norm.size(0)) != B:
+        raise ValueError(f"question_embedding_norm holds {int(question_embedding_norm.size(0))} rows for {B} graphs")
+    dev = _dev()
+    e_cnt = np.asarray([0 if untouched[g] else srcs[g].shape[0] for g in range(B)], np.int64)
+    edge_ptr_h = np.concatenate([[0], np.cumsum(e_cnt)]).astype(np.int64)
+    live = [g for g in range(B) if not untouched[g]]
+    cat = lambda parts, dt: np.concatenate(parts).astype(dt) if parts else np.empty(0, dt)  # noqa: E731
+    for g in live:
+        if len(edge_dst[g]) != e_cnt[g] or len(edge_relation_ids[g]) != e_cnt[g] or masks[g].shape[0] != e_cnt[g]:
+            raise ValueError(f"graph {g}: edge_src, edge_dst, edge_relation_ids and positive_mask differ in length")
+    # node ids stay graph-local: only edges of one graph are compared, so no offset is needed
+    ei = np.stack([cat([srcs[g] for g in live], np.int64), cat([np.asarray(edge_dst[g], np.int64).reshape(-1) for g in live], np.int64)])
+    rel = cat([np.asarray(edge_relation_ids[g], np.int64).reshape(-1) for g in live], np.int64)
+    mask = cat([masks[g] for g in live], np.uint8)
+    # pair slots: a graph with empty lists (or an untouched one) contributes none
+    paired = [g for g in live if len(pair_edge_local_ids[g]) and len(pair_edge_counts[g])]
+    cnts = [np.asarray(pair_edge_counts[g], np.int64).reshape(-1) for g in paired]
+    ids = [np.asarray(pair_edge_local_ids[g], np.int64).reshape(-1) for g in paired]
+    for g, c, i in zip(paired, cnts, ids):
+        if int(c.sum()) != i.shape[0]:
+            raise ValueError("pair_edge_counts do not sum to len(pair_edge_local_ids)")
+        if i.shape[0] and (int(i.min()) < 0 or int(i.max()) >= e_cnt[g]):
+            raise IndexError(f"graph {g}: pair_edge_local_ids outside [0, {int(e_cnt[g])})")
+    pair_cnt = cat(cnts, np.int32)
+    pair_ids = cat([i + edge_ptr_h[g] for g, i in zip(paired, ids)], np.int64)
+    pair_off = np.concatenate([[0], np.cumsum(pair_cnt, dtype=np.int64)]).astype(np.int64)
+    P, E = pair_cnt.shape[0], int(edge_ptr_h[-1])
+    d_ei, d_rel, d_eptr, d_off, d_ids, d_cnt, d_mask = _upload_packed(dev, [ei.reshape(-1), rel, edge_ptr_h, pair_off, pair_ids, pair_cnt, mask])
+    z = np.empty(0, np.int64)
+    pair_graph_h = np.repeat(np.asarray(paired, np.int64), [c.shape[0] for c in cnts]) if paired else z
+    flat = FlatPairLabels(B, E, edge_ptr_h, d_mask, torch.zeros(P, dtype=torch.int32, device=dev), d_cnt, d_off, d_ids, pair_graph_h,
+                          np.zeros(P, np.int64), np.zeros(P, np.int64), np.zeros(B + 1, np.int64), edge_ptr=d_eptr)
+    out = canonicalize_flat(flat, d_ei.view(2, E), d_rel, question_embedding_norm.to(dev), relation_embeddings_norm.to(dev))
+    # one read-back: status, counts, ids and the keep mask as the bytes of one buffer
+    back = torch.cat([out.status.view(torch.uint8), out.pair_count.view(torch.uint8), out.pair_edge_ids.view(torch.uint8),
+                      out.mask[:E]]).cpu().numpy()
+    st = int(back[:4].view(np.int32)[0])
+    if st & 1:
+        raise IndexError("edge_relation_ids outside [0, num_relations) on a positive edge that had to be scored")
+    if st & 2:
+        raise ValueError("a relation score is not finite (NaN or inf in the normalised embeddings)")
+    new_cnt = back[4: 4 + 4 * P].view(np.int32).astype(np.int64)
+    new_ids = back[4 + 4 * P: 4 + 4 * P + 8 * pair_ids.shape[0]].view(np.int64)
+    keep_h = back[4 + 4 * P + 8 * pair_ids.shape[0]:].astype(bool)
+    new_off = np.concatenate([[0], np.cumsum(new_cnt)]).astype(np.int64)
+    p_ptr = np.concatenate([[0], np.cumsum([c.shape[0] for c in cnts])]).astype(np.int64)
+    slot_of = {g: k for k, g in enumerate(paired)}
+    results = []
+    for g in range(B):
+        if untouched[g]:
+            results.append((list(positive_mask[g]), list(pair_edge_local_ids[g]), list(pair_edge_counts[g])))
+            continue
+        km = keep_h[int(edge_ptr_h[g]): int(edge_ptr_h[g + 1])].tolist()
+        if g not in slot_of:
+            results.append((km, list(pair_edge_local_ids[g]), list(pair_edge_counts[g])))
+            continue
+        p0, p1 = int(p_ptr[slot_of[g]]), int(p_ptr[slot_of[g] + 1])
+        results.append((km, (new_ids[int(new_off[p0]): int(new_off[p1])] - edge_ptr_h[g]).tolist(), new_cnt[p0:p1].tolist()))
+    return results
+
+
 # ---- GAgentBuilder statics ---------------------------------------------------------------------------
 
 def node_softmax_logit(*, edge_scores: torch.Tensor, edge_head_locals: torch.Tensor, edge_tail_locals: torch.Tensor,
@@ -569,7 +728,8 @@ def seed_onehop_stats(heads: torch.Tensor, tails: torch.Tensor, labels: torch.Te
     return [(int(s), int(d), int(p)) for s, d, p in zip(uniq.tolist(), deg.tolist(), pdeg.tolist()) if d >= 0]
 
 
-__all__ = ["GraphBatch", "FlatPairLabels", "label_pairs_flat", "canonicalize_positive_edges", "bfs_dist", "bfs_dist_batch", "shortest_path_union_mask_by_pair",
+__all__ = ["GraphBatch", "FlatPairLabels", "label_pairs_flat", "canonicalize_positive_edges", "CanonicalPairLabels", "canonicalize_flat",
+           "canonicalize_positive_edges_batch", "bfs_dist", "bfs_dist_batch", "shortest_path_union_mask_by_pair",
            "shortest_path_single", "shortest_path_single_batch", "has_connectivity",
            "shortest_path_union_mask_by_pair_batch", "node_softmax_logit", "select_topk_edges", "select_start_edges",
            "seed_onehop_stats"]

@@ -460,6 +460,34 @@ int evi_shortest_path_pairs(int pass, const int32_t* pair_graph, const int32_t* 
                             int32_t* pair_edge_count, uint8_t* edge_mask, const int64_t* pair_edge_off,
                             int64_t* pair_edge_ids, void* stream);
 
+/* Canonical positive edges of a whole batch (C2-C4): among the parallel positive edges of one unordered node pair
+ * (min(u, v), max(u, v)) — (u, v) and (v, u) share a group, a self loop's key is (u, u) — exactly one survives: the one with the
+ * largest relation_norm[rel[e]] . question_norm[g]; ties go to the smallest (relation id, edge id); a group of one keeps its edge
+ * unscored.  Inputs as they lie in a collated batch and in the outputs of evi_shortest_path_pairs: edge_index [2, E] i64
+ * batch-global, edge_ptr [B + 1], edge_relation_ids [E], mask [E] u8 (positive edges, not modified), pair_count [P],
+ * pair_edge_off [P + 1], pair_edge_ids (batch-global edge ids), question_norm [B, D] f32, relation_norm [R, D] f32.
+ *   pass 0: keep[e] (all of [0, E) is written: 1 for the surviving positives, else 0) and new_pair_count[p] = the ids of pair p's
+ *           span whose keep is 1 (an id outside [0, E) is dropped);
+ *   pass 1: those ids in the span's order at new_pair_edge_ids[new_pair_edge_off[p] ...] (the caller's exclusive cumsum of
+ *           new_pair_count).
+ * A score is a function of the two rows' bytes alone (fixed lane assignment, fixed reduction tree, the same operations whether
+ * rows are read as 16-byte vectors — D % 4 == 0 and 16-byte aligned tables — or as scalars), so edges with one relation id, and
+ * relation rows with identical bytes, tie exactly.  Only members of groups of two or more are scored.  One workgroup per graph;
+ * up to evi_canonical_edges_lds_capacity() positives of a graph are grouped in LDS, more in the workspace
+ * (evi_canonical_edges_workspace_bytes, a function of the sizes only), with the same result.  Deferred faults are OR-ed into
+ * *status (the caller zeroes it): bit 0 a relation id outside [0, R) on a scored edge (scored clamped, nothing outside the
+ * table is read), bit 1 a score that is not finite.
+ * Replaces _group_positive_edges_by_pair / _select_canonical_edge_indices / _filter_pair_edges,
+ * scripts/build_retrieval_pipeline.py:840-932. */
+int evi_canonical_edges_lds_capacity(void);
+size_t evi_canonical_edges_workspace_bytes(int64_t E, int B, int D);
+int evi_canonical_edges(int pass, const int64_t* edge_index, int64_t E, const int64_t* edge_ptr, int B,
+                        const int64_t* edge_relation_ids, const uint8_t* mask, const int32_t* pair_count,
+                        const int64_t* pair_edge_off, const int64_t* pair_edge_ids, int num_pairs,
+                        const float* question_norm, const float* relation_norm, int64_t R, int D, uint8_t* keep,
+                        int32_t* new_pair_count, const int64_t* new_pair_edge_off, int64_t* new_pair_edge_ids,
+                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The reference's deterministic single shortest path between a source set and a target set over the
  * undirected graph (G4).  Job j works on graph job_graph[j] with batch-global sources
  * src_idx[src_ptr[j]..) and targets tgt_idx[tgt_ptr[j]..) (out-of-range ids are ignored) and uses
